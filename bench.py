@@ -2,6 +2,7 @@
 """Headline benchmark of the CXRMate hot path on MI355X (contract: README of the build driver).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR    # + what the last timed TF step computed, as DIR/*.npy
     python bench.py --gpus N ...                                  # no torchrun environment: starts N ranks itself (before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -54,7 +55,7 @@ def decode_step_bytes(rows, studies, n_images, t_ctx, layers=6, d=768, vocab=300
 
 
 # CXR_BENCH_REHEARSAL=1: the SAME control flow (rank spawn, affinity masks, rendezvous, per-rank seeds, barriers, max-over-ranks timing, all-reduces,
-# the SCST gather, the one JSON line of rank 0) on the tiny parity-test configuration, so that `bench.py --gpus 8` can be rehearsed with 8 ranks
+# the SCST gather, the one JSON line of rank 0) on the tiny parity-test configuration, so that `bench.py --gpus N` can be rehearsed with N ranks
 # sharing ONE GPU (CXR_SINGLE_DEVICE=1 CXR_DIST_BACKEND=gloo) -- tests/test_dp_gpu.py. The line it prints says "rehearsal": it is never a number.
 REHEARSAL = os.environ.get("CXR_BENCH_REHEARSAL") == "1"
 IMG = 96 if REHEARSAL else 384
@@ -462,9 +463,12 @@ def _scst_string_steps(args, model, opt, images, prompt, special, dev, B, reward
                     "one 48-row CXR-BERT forward (sampled + greedy + this step's label rows); synthetic byte-BPE tokenizer (tests/golden/tokenizer.json) on the random-init model's strings"}
 
 
-def tf_bench(args, rank, world, dev, model, n_images, steps, profile_gemm):
+DUMP_SAMPLE = 1 << 22          # master weights written by --dump-outputs: this many (16 MB of fp32), drawn with replacement, seed 0
+
+
+def tf_bench(args, rank, world, dev, model, n_images, steps, profile_gemm, dump=False):
     """One teacher-forcing optimisation step = forward, CE, backward, (all-reduce,) AdamW. -> dict with tokens/s, ms/step and, optionally, the
-    live GEMM profile."""
+    live GEMM profile and (dump=True) what the last timed step handed back: its loss and a fixed sample of the updated fp32 master weights."""
     from cxrmate_amd import ops
     from cxrmate_amd.training import FusedAdamW, GraphedTFStep, tf_train_step
     B, T, V = args.batch, args.seq_len, model.config.decoder.vocab_size
@@ -486,20 +490,24 @@ def tf_bench(args, rank, world, dev, model, n_images, steps, profile_gemm):
         graphed = GraphedTFStep(model, opt, px, inp, am, tt, lab, pad_token_id=4)          # hipGraph capture (3 segments)
         step = lambda: graphed(px, inp, am, tt, lab)
     # untimed pre-warm-up: lazy kernel loading, caching-allocator growth on both streams, first-use buffers (transposed weights, LoRA merges)
-    # and the device itself -- the first ~second of work on a fresh box runs 5-8 % slow, which 3 warm-up steps do not cover. At least 2 steps
-    # and 1.5 s of them; the W requested warm-up steps follow.
-    t_pre, n_pre = time.perf_counter(), 0
-    n_fixed = int(os.environ.get("CXR_BENCH_PREWARM", "32"))          # world > 1 only (a rehearsal of the multi-rank flow on one GPU sets it to 2)
-    while (n_pre < n_fixed) if world > 1 else (n_pre < 2 or (time.perf_counter() - t_pre < 1.5 and n_pre < 64)):
-        step()                              # (every rank must run the SAME number of steps -- each one all-reduces: fixed count when world > 1)
+    # and the device itself -- the first ~second of work on a fresh box runs 5-8 % slow, which 3 warm-up steps do not cover. A FIXED number of
+    # steps (40 = ~1.6 s of the 39.5 ms headline step on one GPU), so that the same arguments put the same model state into the timed steps
+    # (--dump-outputs) and every rank runs as many steps as the others (each one all-reduces); the W requested warm-up steps follow.
+    n_fixed = int(os.environ.get("CXR_BENCH_PREWARM", "32" if world > 1 else "40"))     # (a rehearsal of the multi-rank flow on one GPU sets 2)
+    for n_pre in range(n_fixed):
+        step()
         if n_pre % 4 == 3:
             torch.cuda.synchronize()
-        n_pre += 1
     for _ in range(args.warmup):
         step()
     dt, loss = timed(step, steps, world, dev)
     res = {"ms_per_step": dt / steps * 1e3, "tokens_per_s": world * B * T * steps / dt, "loss": float(loss.item()),
            "step_gflop_per_gpu": 3.0 * (ENC_FWD_GF_PER_IMAGE * n_images + dec_fwd_gf(n_images, T)) * B}
+    if dump:                                # before the profiled step below moves the weights on
+        w = model.flat32[: model._param_total]
+        idx = torch.randint(0, w.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).to(w.device)
+        res["dump"] = {"tf_loss": loss.detach().float().reshape(-1).cpu().numpy(),
+                       "tf_master_weights_sample": w[idx].float().cpu().numpy()}
     if profile_gemm:
         # dominant kernel = gemm_nt_kernel (bf16 MFMA): live HIP-event timing of every launch in one extra step
         ops.GEMM_PROFILE = []
@@ -698,7 +706,11 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the TF step from hipGraphs (3 segments)")
     ap.add_argument("--eval-mode", action="store_true", help="run the steps under model.eval() (running-statistics BatchNorm, no dropout)")
     ap.add_argument("--new-tokens", type=int, default=255)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed teacher-forcing step computed as DIR/<name>.npy "
+                    "(fp32: its loss and a fixed, seeded sample of the updated master weights)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
 
@@ -726,6 +738,9 @@ def main():
         raise SystemExit(f"bench.py --gpus {args.gpus} but the process group has {world} rank(s): refusing to report a {world}-GPU number")
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    # the train-mode steps draw their dropout / DropPath seeds from torch's generator, which otherwise starts from a different seed in every
+    # process: seeded per rank (like the synthetic batch), the same arguments give the same masks, and --dump-outputs the same arrays
+    torch.manual_seed(1000 + rank)
 
     from cxrmate_amd.config import EncoderDecoderConfig
     from cxrmate_amd.modelling import MultiCXREncoderDecoderModel, SingleCXREncoderDecoderModel
@@ -736,7 +751,12 @@ def main():
     model = (MultiCXREncoderDecoderModel if N > 1 else SingleCXREncoderDecoderModel)(cfg, device=dev, seed=0)
     if not args.eval_mode:
         model.train()
-    main_res = tf_bench(args, rank, world, dev, model, N, args.steps, profile_gemm=True)
+    main_res = tf_bench(args, rank, world, dev, model, N, args.steps, profile_gemm=True, dump=bool(args.dump_outputs) and rank == 0)
+    if "dump" in main_res:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in main_res.pop("dump").items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     ms_per_step, tokens_per_s = main_res["ms_per_step"], main_res["tokens_per_s"]
     gm = main_res["gemm"]
     traffic, traffic_src = None, None                        # HBM-side bytes per launch from the committed PMC passes (cannot be collected live)

@@ -13,6 +13,10 @@ import golden_util as gu
 
 pytestmark = pytest.mark.gpu
 
+# Ranks of the multi-rank rehearsals below. They all open the one GPU beside this pytest process, and the shared test machines allow at most
+# six processes with the GPU open at a time: four ranks + the parent (+ bench.py's launcher, which never touches the GPU) stay within it.
+REHEARSAL_RANKS = 4
+
 
 def _worker(rank, world, path, q):
     import torch.distributed as dist
@@ -324,7 +328,7 @@ def test_rccl_backend_executes_the_reducer_and_the_gather_at_world_1():
 
 
 def _rehearsal_worker(rank, world, path, q):
-    """One of EIGHT ranks sharing the one visible GPU (gloo on device tensors): two accumulated TF optimiser steps with the collective log, then
+    """One of REHEARSAL_RANKS ranks sharing the one visible GPU (gloo on device tensors): two accumulated TF optimiser steps with the collective log, then
     one train-mode SCST step on the same replica family (a longitudinal model of its own)."""
     import torch.distributed as dist
     from cxrmate_amd import modelling
@@ -335,10 +339,10 @@ def _rehearsal_worker(rank, world, path, q):
 
     def phase(name):
         if rank == 0 and os.environ.get("CXR_TEST_PHASES"):
-            print(f"[dp8 rank 0] {name}: {time.time() - t_start:.1f} s", flush=True)
+            print(f"[dp rank 0] {name}: {time.time() - t_start:.1f} s", flush=True)
 
     try:
-        torch.set_num_threads(1)                                      # eight ranks share this host's cores
+        torch.set_num_threads(1)                                      # the ranks share this host's cores
         dist.init_process_group("gloo", init_method=f"file://{path}", rank=rank, world_size=world)
         torch.cuda.set_device(0)
         phase("process group up")
@@ -369,7 +373,7 @@ def _rehearsal_worker(rank, world, path, q):
         ml = modelling.LongitudinalPromptMultiCXREncoderDecoderModel(cfl, device="cuda:0", seed=None)
         ml.load_state_dict(torch.load(os.path.join(os.path.dirname(path), "scst.pt")))
         ml.train()
-        ml.graph_decode = False                                       # (eight captures of the same step graphs would only cost test time)
+        ml.graph_decode = False                                       # (one capture of the same step graphs per rank would only cost test time)
         for p in ml.decoder.parameters():
             p.requires_grad_(True)
         optl = FusedAdamW(ml, lr=1e-3)
@@ -393,15 +397,15 @@ def _rehearsal_worker(rank, world, path, q):
             dist.destroy_process_group()
 
 
-def test_dp8_rehearsal_on_one_device():
-    """What can be proven about 8 ranks without an 8-GPU node (this build has never had one: NO scaling curve exists): EIGHT processes share the
-    one GPU (gloo on device tensors) and run the data-parallel TF step under accumulate=(j, 2) and the train-mode SCST step. Every rank issues the
-    same collective sequence (a different order deadlocks or mixes buckets on RCCL), the replicas are bit-identical afterwards, and
-    gather_scst_statistics returns 8 x B records in rank order. Reference: config/train/single_tf.yaml:8 (`strategy: ddp`), data/prompt.py:142-213."""
+def test_dp_rehearsal_ranks_share_one_device():
+    """What can be proven about several ranks without a multi-GPU node (this build has never had one: NO scaling curve exists): REHEARSAL_RANKS
+    processes share the one GPU (gloo on device tensors) and run the data-parallel TF step under accumulate=(j, 2) and the train-mode SCST step.
+    Every rank issues the same collective sequence (a different order deadlocks or mixes buckets on RCCL), the replicas are bit-identical
+    afterwards, and gather_scst_statistics returns world x B records in rank order. Reference: config/train/single_tf.yaml:8 (`strategy: ddp`), data/prompt.py:142-213."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import torch.multiprocessing as mp
-    world = 8
+    world = REHEARSAL_RANKS
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     from cxrmate_amd import weights
@@ -420,7 +424,7 @@ def test_dp8_rehearsal_on_one_device():
     _, _, log0, marks0, tfw0, sw0, gs0, gr0, _, rw0 = res[0]
     assert marks0[0] == 0 and marks0[2] == marks0[1] and len(log0) == 2 * marks0[1] and marks0[1] == 4      # decoder | stage 2 + head | stage 1 | stage 0
     for r in res[1:]:
-        assert r[2] == log0 and r[3] == marks0                          # identical collective order on all 8 ranks
+        assert r[2] == log0 and r[3] == marks0                          # identical collective order on all ranks
         assert np.array_equal(r[4], tfw0)                               # TF replicas bit-identical after two accumulated steps
         assert np.array_equal(r[5], sw0)                                # SCST replicas (LoRA included) bit-identical
         assert np.array_equal(r[6], gs0) and np.array_equal(r[7], gr0) and r[9] == rw0          # the same global view everywhere
@@ -431,10 +435,11 @@ def test_dp8_rehearsal_on_one_device():
     assert len({r[8].tobytes() for r in res}) > 1                        # per-rank random streams / studies
 
 
-def test_bench_gpus_8_rehearsal_and_refusal():
-    """`bench.py --gpus 8` end to end with 8 ranks on the one GPU (CXR_BENCH_REHEARSAL=1: tiny configuration; gloo; every rank on device 0): spawn_ranks
-    finds a port, hands each rank its slice of the host cores, the ranks rendezvous, run the TF and SCST keys with their all-reduces / gather, and
-    rank 0 prints ONE JSON line for n_gpus = 8 that says it is a rehearsal. A process group whose size is not N is refused."""
+def test_bench_multi_gpu_rehearsal_and_refusal():
+    """`bench.py --gpus N` end to end with N = REHEARSAL_RANKS ranks on the one GPU (CXR_BENCH_REHEARSAL=1: tiny configuration; gloo; every rank on
+    device 0): spawn_ranks finds a port, hands each rank its slice of the host cores, the ranks rendezvous, run the TF and SCST keys with their
+    all-reduces / gather, and rank 0 prints ONE JSON line for n_gpus = N that says it is a rehearsal. A process group whose size is not N is
+    refused (`--gpus 8` in a one-rank environment)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import json
@@ -444,13 +449,14 @@ def test_bench_gpus_8_rehearsal_and_refusal():
     env = dict(os.environ, CXR_BENCH_REHEARSAL="1", CXR_SINGLE_DEVICE="1", CXR_DIST_BACKEND="gloo", CXR_BENCH_PREWARM="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "0", "--batch", "2", "--seq-len", "16",
+    n = REHEARSAL_RANKS
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "0", "--batch", "2", "--seq-len", "16",
                         "--scst-steps", "1", "--new-tokens", "9", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                               # ONE line, from rank 0
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["config"]["rccl_ranks"] == 8 and out["config"]["global_batch"] == 16 and "rehearsal" in out
+    assert out["n_gpus"] == n and out["config"]["rccl_ranks"] == n and out["config"]["global_batch"] == 2 * n and "rehearsal" in out
     assert out["scaling"] == "weak" and out["value"] > 0 and np.isfinite(out["config"]["loss"])
     assert out["scst"]["value"] and np.isfinite(out["scst"]["loss"])
     # refusal: a one-rank environment asked for an 8-GPU number
@@ -458,3 +464,44 @@ def test_bench_gpus_8_rehearsal_and_refusal():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"], env=env1, capture_output=True,
                        text=True, timeout=600, cwd=root)
     assert r.returncode != 0 and "refusing to report" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` (tiny rehearsal configuration, one rank): after the timed steps it writes the loss of the last timed TF step
+    and a fixed sample of the master weights it left, as fp32 .npy files under 64 MB, and the result line reports the requested step count with
+    `ms_per_step`. Two runs with the same arguments start the timed steps from the same state (same batch, weights and dropout masks), so they
+    write the same loss up to rounding, and weights no further apart than AdamW's steps allow: the embedding and LayerNorm weight gradients are
+    summed with float atomics, whose order varies from run to run, and AdamW can turn a gradient that is only rounding noise into a step of up to
+    +-lr. (Other dropout masks move this loss by ~1 %; other initial weights move the weights by their own scale, ~0.02.)"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CXR_BENCH_REHEARSAL="1", CXR_BENCH_PREWARM="2")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--seq-len", "16",
+                            "--no-scst", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)], env=env, capture_output=True, text=True,
+                           timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["tf_loss.npy", "tf_master_weights_sample.npy"]
+        arrs = {f: np.load(d / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert np.isclose(float(arrs["tf_loss.npy"][0]), out["config"]["loss"], rtol=1e-6)
+        dumps.append(arrs)
+    l0, l1 = (float(d["tf_loss.npy"][0]) for d in dumps)
+    assert np.isclose(l0, l1, rtol=1e-4, atol=0), (l0, l1)
+    w0, w1 = (d["tf_master_weights_sample.npy"] for d in dumps)
+    lr, updates = 5e-5, 2 + 1 + 3                                        # tf_bench's AdamW; CXR_BENCH_PREWARM + --warmup + --steps
+    assert np.abs(w0 - w1).max() <= 2 * lr * updates, float(np.abs(w0 - w1).max())
