@@ -230,13 +230,16 @@ class BertEngine:
         return _CROSS_KV_SHARED and bool(self.cfg.add_cross_attention) and self._cross_kv_all() is not None
 
     def forward(self, ids, enc=None, enc_mask=None, attn_mask=None, token_type_ids=None, position_ids=None, save=False, causal=True,
-                lm_head=True, train=None, seed=None, logits_bf16=False, inputs_embeds=None, cross_kv=None, logit_from=0):
+                lm_head=True, train=None, seed=None, logits_bf16=False, inputs_embeds=None, cross_kv=None, logit_from=0, collect=None):
         """ids int64 [B,T]; enc bf16 [B,S,D] | None; masks uint8 (1 = attend). -> logits fp32 [B,T,V] (or hidden bf16 [B,T,D]), saved.
         train (default: the store's nn.Module flag) enables dropout; seed: device int32 [1] to REPRODUCE the masks of an earlier pass.
         cross_kv: [B, S, 2 L D] bf16, the cross-attention K / V of all layers already projected from THIS enc with the current weights (a decode
         session's prefill): the projection GEMM is skipped; the backward is unchanged.
         logit_from = t0 > 0: the LM head runs on positions t0 .. T-1 only -> logits [B, T - t0, V], contiguous (the SCST re-scoring pass scores the
-        sampled positions, not the prompt's; backward(dlogits=[B (T - t0), V]) then)."""
+        sampled positions, not the prompt's; backward(dlogits=[B (T - t0), V]) then).
+        collect: None | a set of {"attn", "hidden"} (output_attentions / output_hidden_states) -> a third return value, a dict with
+        "self_attn" / "cross_attn": per layer fp32 [B, H, T, T] / [B, H, T, S] (post-dropout in train mode, ops.attention_probs) and "hidden":
+        L + 1 fp32 [B, T, D] (embedding output, then each layer's). None: launches and results exactly as without the argument."""
         cfg, st, p = self.cfg, self.s, self.p
         self.prepare()
         lora_tr = self._lora_train(train)
@@ -253,12 +256,17 @@ class BertEngine:
         D, nh = cfg.hidden_size, cfg.num_attention_heads
         R = B * T
         ph, pa, seed = self._dropout_cfg(train, seed)
+        want_attn, want_hidden = collect is not None and "attn" in collect, collect is not None and "hidden" in collect
+        extra = dict(self_attn=[], cross_attn=[], hidden=[]) if collect is not None else None
+        need_lse = save or want_attn
         pl, ls = float(cfg.lora_dropout), (cfg.lora_alpha / cfg.lora_r if cfg.lora_r else 0.0)
         e = p + "bert.embeddings."
         h, esum, estats = ops.bert_embed(ids, token_type_ids, position_ids, st.w16(e + "word_embeddings.weight") if word is None else word,
                                          st.w16(e + "token_type_embeddings.weight"), st.w16(e + "position_embeddings.weight"),
                                          st.f32(e + "LayerNorm.weight"), st.f32(e + "LayerNorm.bias"), cfg.layer_norm_eps, T, need_sum=save,
                                          drop=(ph, seed, SITE_EMBED) if ph else None)
+        if want_hidden:
+            extra["hidden"].append(h)
         saved = dict(B=B, T=T, ids=ids, tt=token_type_ids, pos=position_ids, esum=esum, estats=estats, attn_mask=attn_mask, enc=enc,
                      enc_mask=enc_mask, causal=causal, layers=[], ph=ph, pa=pa, seed=seed, lora_tr=lora_tr, from_embeds=word is not None) if save else None
         scale = cfg.head_dim ** -0.5
@@ -318,7 +326,9 @@ class BertEngine:
                     q = ops.gemm_nt(h, wq, bias=bq).view(B, T, D)
                     k = ops.gemm_nt(h, wk, bias=bk).view(B, T, D)
                     v = ops.gemm_nt(h, wv, bias=bv).view(B, T, D)
-            ctx, lse = ops.attention(q, k, v, nh, scale, kpm=attn_mask, causal=causal, need_lse=save, drop=(pa, seed, _site(l, 0), 0))
+            ctx, lse = ops.attention(q, k, v, nh, scale, kpm=attn_mask, causal=causal, need_lse=need_lse, drop=(pa, seed, _site(l, 0), 0))
+            if want_attn:
+                extra["self_attn"].append(ops.attention_probs(q, k, lse, nh, scale, kpm=attn_mask, causal=causal, drop=(pa, seed, _site(l, 0), 0)))
             wo, bo = self._lin(lp + "attention.output.dense")
             a1 = out_proj(ctx.view(R, D), wo, bo, h, _site(l, 1))
             h1, s1 = ops.layernorm(a1, st.f32(lp + "attention.output.LayerNorm.weight"), st.f32(lp + "attention.output.LayerNorm.bias"),
@@ -335,7 +345,9 @@ class BertEngine:
                 else:
                     k2 = ops.gemm_nt(enc.view(B * S, D), ck, bias=cbk).view(B, S, D)
                     v2 = ops.gemm_nt(enc.view(B * S, D), cv, bias=cbv).view(B, S, D)
-                ctx2, lse2 = ops.attention(q2, k2, v2, nh, scale, kpm=enc_mask, need_lse=save, drop=(pa, seed, _site(l, 2), 0))
+                ctx2, lse2 = ops.attention(q2, k2, v2, nh, scale, kpm=enc_mask, need_lse=need_lse, drop=(pa, seed, _site(l, 2), 0))
+                if want_attn:
+                    extra["cross_attn"].append(ops.attention_probs(q2, k2, lse2, nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), 0)))
                 a2 = out_proj(ctx2.view(R, D), co, cbo, h1, _site(l, 3))
                 h2, s2 = ops.layernorm(a2, st.f32(lp + "crossattention.output.LayerNorm.weight"), st.f32(lp + "crossattention.output.LayerNorm.bias"),
                                        cfg.layer_norm_eps, need_stats=save)
@@ -351,10 +363,14 @@ class BertEngine:
             if save:
                 sv.update(u=u, f=f, a3=a3, s3=s3, h2in=h2)
                 saved["layers"].append(sv)
+            if want_hidden:
+                extra["hidden"].append(h)
+        if want_hidden:
+            extra["hidden"] = [ops.cast_to_f32(x).view(B, T, D) for x in extra["hidden"]]
         if not lm_head:
             if save:
                 saved["h_out"] = h
-            return h.view(B, T, D), saved
+            return (h.view(B, T, D), saved) if extra is None else (h.view(B, T, D), saved, extra)
         t0 = int(logit_from)
         if t0 > 0:
             assert t0 < T
@@ -366,6 +382,8 @@ class BertEngine:
         logits, hs = self._lm_head(hl, save, logits_bf16)
         if save:
             saved.update(h_out=hl, logit_from=t0, **hs)
+        if extra is not None:
+            return logits.view(B, T - t0, -1), saved, extra
         return logits.view(B, T - t0, -1), saved
 
     def _lm_head(self, h, save, logits_bf16=False):

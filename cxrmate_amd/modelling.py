@@ -31,12 +31,16 @@ from .token_helpers import TokenHelpers
 
 class ModelOutput(dict):
     """Minimal stand-in for transformers' ModelOutput: attribute, key and integer access; item assignment
-    (the SCST caller does `sample['sequences'] = ...`, reference scst/gt_prompt.py:185-186)."""
+    (the SCST caller does `sample['sequences'] = ...`, reference scst/gt_prompt.py:185-186). The optional Seq2SeqLMOutput fields below are
+    keys only when they were asked for (output_attentions / output_hidden_states), as in transformers; as attributes they read None otherwise."""
+    _OPTIONAL = ("decoder_hidden_states", "decoder_attentions", "cross_attentions")
 
     def __getattr__(self, k):
         try:
             return self[k]
         except KeyError:
+            if k in ModelOutput._OPTIONAL:
+                return None
             raise AttributeError(k)
 
     def __setattr__(self, k, v):
@@ -252,17 +256,24 @@ class _EncodeFn(torch.autograd.Function):
 
 class _DecodeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, enc, enc_mask, ids, attn_mask, tt, pos, seed, embeds, cross_kv, logit_from, *params):
+    def forward(ctx, model, enc, enc_mask, ids, attn_mask, tt, pos, seed, embeds, cross_kv, logit_from, collect, *params):
         model._settle_owed_join()
-        logits, saved = model._dec.forward(ids, enc, enc_mask, attn_mask, tt, pos, save=True, seed=seed, inputs_embeds=embeds, cross_kv=cross_kv,
-                                           logit_from=logit_from)
+        out = model._dec.forward(ids, enc, enc_mask, attn_mask, tt, pos, save=True, seed=seed, inputs_embeds=embeds, cross_kv=cross_kv,
+                                 logit_from=logit_from, collect=collect)
+        logits, saved = out[0], out[1]
         ctx.model, ctx.saved, ctx.nparams = model, saved, len(params)
         ctx.need_denc = enc is not None and enc.requires_grad
         ctx.embeds_like = embeds if (embeds is not None and embeds.requires_grad) else None
-        return logits
+        if collect is None:
+            return logits
+        # output_attentions / output_hidden_states: extra outputs, detached (no gradient flows through the returned maps or states)
+        extra = out[2]
+        maps = (*extra["hidden"], *extra["self_attn"], *extra["cross_attn"])
+        ctx.mark_non_differentiable(*maps)
+        return (logits, *maps)
 
     @staticmethod
-    def backward(ctx, dlogits):
+    def backward(ctx, dlogits, *_maps):
         model = ctx.model
         bound = model._grads_bindable("decoder.")
         if not model.direct_grads and bound != "accumulate":
@@ -282,8 +293,8 @@ class _DecodeFn(torch.autograd.Function):
             d_emb = ctx.saved["d_embeds"].view(ctx.embeds_like.shape).to(ctx.embeds_like.dtype)
         ctx.saved = None
         if bound:
-            return (None, denc, None, None, None, None, None, None, d_emb, None, None) + model._bind_grads("decoder.", ctx.nparams)
-        return (None, denc, None, None, None, None, None, None, d_emb, None, None) + model._collect_grads("decoder.", ctx.nparams)
+            return (None, denc, None, None, None, None, None, None, d_emb, None, None, None) + model._bind_grads("decoder.", ctx.nparams)
+        return (None, denc, None, None, None, None, None, None, d_emb, None, None, None) + model._collect_grads("decoder.", ctx.nparams)
 
 
 # ---------------------------------------------------------------------------------------------------- sub-modules
@@ -593,8 +604,12 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         if past_key_values is not None:
             return self._forward_cached(decoder_input_ids, enc, enc_mask, decoder_attention_mask, kwargs_decoder, past_key_values, labels,
                                         decoder_inputs_embeds, return_dict)
+        collect = {k for k, on in (("attn", output_attentions), ("hidden", output_hidden_states)) if on} or None
         logits = self._decode_tf(decoder_input_ids, enc, enc_mask, decoder_attention_mask, kwargs_decoder.get("token_type_ids"),
-                                 kwargs_decoder.get("position_ids"), embeds=decoder_inputs_embeds)
+                                 kwargs_decoder.get("position_ids"), embeds=decoder_inputs_embeds, collect=collect)
+        extra = None
+        if collect is not None:
+            logits, extra = logits
         loss = None
         if labels is not None:
             loss = _CrossEntropyFn.apply(logits, labels.to(logits.device), -100)    # CrossEntropyLoss(): mean over labels != -100 (reference :239-241)
@@ -607,7 +622,15 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
             # cache is built by the cached-step kernels' prefill over the same inputs (its last-position logits are not needed). Under autograd no
             # cache is returned (the cached kernels have no backward): the call is then an ordinary teacher-forced pass, as in training.
             past = self._forward_cached(decoder_input_ids, enc, enc_mask, decoder_attention_mask, kwargs_decoder, None, None, None, True).past_key_values
-        out = ModelOutput(loss=loss, logits=logits, past_key_values=past, encoder_last_hidden_state=enc)
+        # Seq2SeqLMOutput field order; the maps and states are keys only when asked for, so a default call has the keys and tuple it always had
+        out = ModelOutput(loss=loss, logits=logits, past_key_values=past)
+        if output_hidden_states:
+            out["decoder_hidden_states"] = tuple(extra["hidden"])
+        if output_attentions:
+            out["decoder_attentions"] = tuple(extra["self_attn"])
+            if extra["cross_attn"]:
+                out["cross_attentions"] = tuple(extra["cross_attn"])
+        out["encoder_last_hidden_state"] = enc
         if return_dict is False:
             return out.to_tuple()
         return out
@@ -651,7 +674,8 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
             return None
         return t.to(device=device, dtype=torch.int64).contiguous()
 
-    def _decode_tf(self, ids, enc, enc_mask, attn_mask, tt, pos, seed=None, embeds=None, cross_kv=None, logit_from=0):
+    def _decode_tf(self, ids, enc, enc_mask, attn_mask, tt, pos, seed=None, embeds=None, cross_kv=None, logit_from=0, collect=None):
+        """-> logits; collect (BertEngine.forward): -> (logits, {"hidden", "self_attn", "cross_attn": lists of fp32 tensors, no gradient})"""
         dev = self.device
         ids, tt, pos = self._i64(ids, dev), self._i64(tt, dev), self._i64(pos, dev)
         if embeds is not None:
@@ -661,10 +685,16 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         enc = enc.contiguous()
         params = [p for _, p in self._grad_params("decoder.")]
         if torch.is_grad_enabled() and (params or enc.requires_grad or (embeds is not None and embeds.requires_grad)):
-            return _DecodeFn.apply(self, enc, enc_mask, ids, attn_mask, tt, pos, seed, embeds, cross_kv, int(logit_from), *params)
-        logits, _ = self._dec.forward(ids, enc, enc_mask, attn_mask, tt, pos, save=False, seed=seed, inputs_embeds=embeds, cross_kv=cross_kv,
-                                      logit_from=logit_from)
-        return logits
+            out = _DecodeFn.apply(self, enc, enc_mask, ids, attn_mask, tt, pos, seed, embeds, cross_kv, int(logit_from), collect, *params)
+            if collect is None:
+                return out
+            L = self.config.decoder.num_hidden_layers
+            nh, ns = L + 1 if "hidden" in collect else 0, L if "attn" in collect else 0
+            nc = len(out) - 1 - nh - ns
+            return out[0], dict(hidden=list(out[1:1 + nh]), self_attn=list(out[1 + nh:1 + nh + ns]), cross_attn=list(out[1 + nh + ns:1 + nh + ns + nc]))
+        out = self._dec.forward(ids, enc, enc_mask, attn_mask, tt, pos, save=False, seed=seed, inputs_embeds=embeds, cross_kv=cross_kv,
+                                logit_from=logit_from, collect=collect)
+        return out[0] if collect is None else (out[0], out[2])
 
 
 class SingleCXREncoderDecoderModel(_CXREncoderDecoderBase):

@@ -478,6 +478,28 @@ def attention(q, k, v, heads, scale, kpm=None, causal=False, causal_shift=None, 
     return out, lse
 
 
+def attention_probs(q, k, lse, heads, scale, kpm=None, causal=False, causal_shift=None, drop=None, out=None):
+    """The probabilities behind attention(q, k, ..., need_lse=True) -> fp32 [B, H, Tq, Tk] (output_attentions): exp(scale q.k - lse) with the
+    same masks; drop = the forward's (p, seed, site, t0) gives its post-dropout maps (keep / (1 - p)), so einsum(P, V) is its context."""
+    B, Tq, D = q.shape
+    Tk = k.shape[1]
+    assert D == heads * 64 and k.shape[0] == B and k.shape[2] == D
+    for t in (q, k):
+        assert t.dtype == BF16 and t.stride(2) == 1
+    assert lse is not None and lse.dtype == torch.float32 and lse.shape == (B, heads, Tq) and lse.is_contiguous()
+    if out is None:
+        out = torch.empty((B, heads, Tq, Tk), device=q.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (B, heads, Tq, Tk) and out.stride(3) == 1
+    if kpm is not None:
+        assert kpm.dtype == torch.uint8 and kpm.shape == (B, Tk) and kpm.stride(1) == 1
+    if causal_shift is None:
+        causal_shift = Tk - Tq
+    LIB.call("cxr_attn_probs_f32", _p(q), _p(k), _p(lse), _p(kpm), _p(out), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+             kpm.stride(0) if kpm is not None else 0, out.stride(0), out.stride(1), out.stride(2), B, heads, Tq, Tk, float(scale), int(causal),
+             int(causal_shift), *_drop_args(drop), _s())
+    return out
+
+
 def attention_q8(q, k, v, heads, scale, out_scale, kpm=None, causal=False, causal_shift=None):
     """attention whose only consumer is an e4m3 GEMM with input scale `out_scale`: -> e4m3 [B, Tq, D] holding bf16(context) / out_scale."""
     B, Tq, D = q.shape

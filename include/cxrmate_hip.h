@@ -114,6 +114,14 @@ int cxr_attn_bwd_bf16(const void* Q, const void* K, const void* V, const void* O
 /* kernel generation behind the two entry points above (A/B measurements, parity tests): forward 1 = 32 query rows per wave, two barriers per tile
  * (rounds 1-2); 2 = 64 rows per wave, double-buffered tiles, one barrier (round 3, default). Backward likewise. Any other value keeps the setting. */
 int cxr_attn_config(int fwd_version, int bwd_version);
+/* attention probabilities as fp32 P[B,H,Tq,Tk] (element (b,h,i,j) at P + b*p_bs + h*p_hs + i*p_rs + j), recomputed from the LSE that
+ * cxr_attn_fwd_bf16 wrote (need_lse) on the same Q / K views, masks and dropout arguments: the softmax and dropout of TF5
+ * eager_attention_forward (TF5:bert:126-131) that output_attentions returns. P = exp(scale * q.k - LSE); entries hidden by kpm or the causal
+ * rule are 0; a row without a visible key is uniform over all Tk keys (finfo.min in the reference); drop_p > 0 applies the forward's keep
+ * mask of (b*H+h, drop_t0 + query, key) and the factor 1/(1-p), so P.V is the context of that forward */
+int cxr_attn_probs_f32(const void* Q, const void* K, const float* LSE, const void* kpm, float* P, long q_bs, long q_rs, long k_bs, long k_rs,
+                       long kpm_bs, long p_bs, long p_hs, long p_rs, int B, int H, int Tq, int Tk, float scale, int causal, int causal_shift,
+                       float drop_p, const unsigned int* drop_seed, unsigned int drop_site, int drop_t0, hipStream_t stream);
 
 /* ---- train-mode dropout / DropPath (TF5:bert:106,298,464; TF5:cvt:297-316) ---------------------------------------------------
  * out = resid + f * y with f = keep(seed, site, b, t, col)/(1-p) per element (b = row / rows_per_b, t = t0 + row % rows_per_b), or
