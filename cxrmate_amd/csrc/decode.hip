@@ -94,6 +94,7 @@ struct BeamArgs {
     int B, nb, V, L, cur, max_length, par, nch;
     long eos;
     float div;                             // (cur + 1 - prompt_len) ^ length_penalty
+    int prenorm;                           // 1: `logits` are already (processed) log-probs, taken as they are (log-sum-exp fixed at 0)
 };
 constexpr int BEAM_CHUNK = 4096;           // vocabulary entries per scan workgroup (16 per thread, held in registers)
 
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
         for (int c = 0; c < nch; ++c) mx = fmaxf(mx, pr[c * (2 + 2 * K2)]);
         float t = 0.f;
         for (int c = 0; c < nch; ++c) t += pr[c * (2 + 2 * K2) + 1] * __expf(pr[c * (2 + 2 * K2)] - mx);
-        off[tid] = mx + __logf(t) - a.run_scores[b * NB + tid];
+        off[tid] = a.prenorm ? -a.run_scores[b * NB + tid] : mx + __logf(t) - a.run_scores[b * NB + tid];
     }
     __syncthreads();
     const int ncand = NB * nch * K2;
@@ -297,15 +298,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
 }
 // div = (cur + 1 - prompt_len) ** length_penalty, evaluated in double by the caller as the library evaluates the Python power, rounded to
 // fp32 as its tensor division does. ws: beams*B * ceil(V / 4096) * (2 + 4*beams) floats.
-extern "C" int cxr_beam_step(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
-                             unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
-                             int max_length, long eos, float div, hipStream_t stream) {
+static int beam_step_launch(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
+                            unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
+                            int max_length, long eos, float div, int prenorm, hipStream_t stream) {
     if (B <= 0 || V <= 0 || cur < 0 || cur >= L || (nb != 1 && nb != 2 && nb != 3 && nb != 4 && nb != 5 && nb != 8) || (long)nb * V >= (1L << 31) || !ws)
         return CXR_ERR_ARG;
     const int nch = cdiv(V, BEAM_CHUNK);
     if (nch > 32) return CXR_ERR_ARG;
     BeamArgs a{logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur, max_length, cur & 1,
-               nch, eos, div};
+               nch, eos, div, prenorm};
     const dim3 sg(nch, nb * B);
 #define BEAM_CASE(NB_) case NB_: CXR_LAUNCH(beam_scan_kernel<2 * NB_>, sg, dim3(256), 0, stream, a);                       \
                                  CXR_LAUNCH(beam_step_kernel<NB_>, dim3(B), dim3(256), 0, stream, a); break
@@ -313,6 +314,20 @@ extern "C" int cxr_beam_step(const float* logits, long ld, long* running, long* 
 #undef BEAM_CASE
     CXR_LAUNCH_CHECK();
     return CXR_OK;
+}
+extern "C" int cxr_beam_step(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
+                             unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
+                             int max_length, long eos, float div, hipStream_t stream) {
+    return beam_step_launch(logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
+                            max_length, eos, div, 0, stream);
+}
+// The same step over log-probs the generation controls have processed (TF5:gen:3388-3389: processors act on log_softmax(logits), nothing
+// renormalises afterwards): candidate score = logprob + running score.
+extern "C" int cxr_beam_step_lp(const float* logprobs, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
+                                unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
+                                int max_length, long eos, float div, hipStream_t stream) {
+    return beam_step_launch(logprobs, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
+                            max_length, eos, div, 1, stream);
 }
 
 // The KV-cache reorder of a beam step for ALL layers in one launch: out[i][r, :rows, :] = in[i][idx[r], :rows, :] for up to 16 tensors of

@@ -118,8 +118,8 @@ class DecodeSession:
 
     def step(self, cur, strip, mode, n=1):
         """Append tokens cur .. cur+n-1 (0-based columns of self.ids). mode = (kind, special_token_ids, mask_token_id, top_k, temperature, eos, pad,
-        train, top_p). The n cached steps are ONE hipGraph (a replay costs ~9 us of launch overhead whatever it holds: per token at n = 1, per
-        8 tokens at n = 8)."""
+        train, top_p, procs); procs = (repetition penalty, n-gram size, absolute min length) of the generation controls, or None. The n cached
+        steps are ONE hipGraph (a replay costs ~9 us of launch overhead whatever it holds: per token at n = 1, per 8 tokens at n = 8)."""
         prefill = self.cache.len == 0
         if prefill or not self.model.graph_decode:
             for c in range(cur, cur + n):
@@ -150,7 +150,7 @@ class DecodeSession:
 
     def _run(self, cur, strip, mode, prefill):
         m = self.model
-        kind, special, mask_token_id, top_k, temperature, eos, pad, train, top_p = mode
+        kind, special, mask_token_id, top_k, temperature, eos, pad, train, top_p, procs = mode
         if prefill:
             fed = self.ids[:, strip:cur]
             new, mask, tt, pos = m._step_inputs(fed, special, mask_token_id, prefill=True)
@@ -179,9 +179,12 @@ class DecodeSession:
         if kind == "beam":                                          # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
             nb, penalty, (prompt_len, max_length) = top_k, temperature, top_p
             st, c = self.beam, self.cache
+            if procs is not None:                                   # TF5 processes log_softmax(logits) on the beam path (utils.py:3388-3389)
+                ops.log_softmax_rows_(logits)
+                ops.logits_process_(logits, self.ids, cur, -1 if eos is None else eos, *procs)
             ops.beam_step(logits, self.ids.view(nb, self.B // nb, self.Lmax), st["sequences"], st["run_scores"], st["beam_scores"], st["finished"],
                           st["unsat"], st["allhit"], st["beam_idx"], cur, max_length, -1 if eos is None else eos,
-                          float(cur + 1 - prompt_len) ** penalty, ws=st["ws"])
+                          float(cur + 1 - prompt_len) ** penalty, ws=st["ws"], logprobs=procs is not None)
             ops.gather_batch_multi(c.k + c.v, st["beam_idx"], c.len, c.k2 + c.v2)
             self._swap_caches()
             self.last_tt = self.last_pos = None
@@ -190,6 +193,8 @@ class DecodeSession:
         eos_ = eos if eos is not None else -1
         n_smp = {"greedy": 0, "sample": self.B, "pair": self.B // 2}[kind]      # rows [0, n_smp) sample, the rest take the argmax
         col = self.ids[:, cur]                                                  # the selection kernels write straight into the id buffer
+        if procs is not None:                                                   # processors before the warpers of select_token (TF5 order)
+            ops.logits_process_(logits, self.ids, cur, eos_, *procs)
         if n_smp:                                                               # one launch for sampled + greedy rows
             u = self.u_all[cur, :n_smp]
             ops.select_token(logits, mode=1, temperature=temperature, top_k=top_k or 0, u=u, unfinished=unf, eos=eos_, pad=pad or 0, out=col,
@@ -243,7 +248,8 @@ class GenerationMixin:
                   special_token_ids=None, mask_token_id=None, max_length=None, max_new_tokens=None, bos_token_id=None,
                   eos_token_id=None, pad_token_id=None, num_beams=1, do_sample=False, top_k=50, top_p=1.0, temperature=1.0,
                   output_scores=False, return_dict_in_generate=False, use_cache=True, length_penalty=1.0, return_margins=False,
-                  forced_tokens=None, record_inputs=False, **unused):
+                  forced_tokens=None, record_inputs=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=None,
+                  num_return_sequences=1, **unused):
         from .modelling import ModelOutput
         if inputs is not None and pixel_values is None:
             pixel_values = inputs
@@ -252,6 +258,19 @@ class GenerationMixin:
         if self.kind == "longitudinal" and mask_token_id is None:
             raise ValueError("mask_token_id is required for the longitudinal model")
         top_p = 1.0 if top_p is None else float(top_p)
+        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        num_beams = 1 if num_beams is None else int(num_beams)
+        if n_ret > 1 and num_beams == 1 and not do_sample:            # TF5 configuration_utils.py:788-805
+            raise ValueError(f"Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` different than 1 "
+                             f"(got {n_ret}).")
+        if num_beams > 1 and n_ret > num_beams:
+            raise ValueError(f"`num_return_sequences` ({n_ret}) has to be smaller or equal to `num_beams` ({num_beams}).")
+        penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if not penalty > 0.0:
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
+        ngram = int(no_repeat_ngram_size or 0)
+        if ngram <= 0 or ngram > ops.LOGITS_PROCESS_MAX_HIST:       # TF5 adds the processor for sizes > 0 only; a size above the longest history
+            ngram = 0                                                # can never complete an n-gram
         with torch.no_grad():
             if encoder_outputs is None:
                 encoder_outputs = self._encode(pixel_values)
@@ -272,6 +291,17 @@ class GenerationMixin:
             max_length = ids.shape[1] + max_new_tokens
         if max_length is None:
             max_length = 20 + ids.shape[1]
+        # generation controls (TF5 logits processors): min_new_tokens takes precedence over min_length as an absolute length (TF5:gen:1760);
+        # EOS bans only while the history is shorter than it, so a minimum the prompt already reaches launches nothing
+        min_abs = (ids.shape[1] + int(min_new_tokens)) if min_new_tokens is not None else int(min_length or 0)
+        min_abs = min_abs if (eos_token_id is not None and min_abs > ids.shape[1]) else 0
+        procs = (penalty, ngram, min_abs) if (penalty != 1.0 or ngram > 0 or min_abs) else None
+        if procs is not None and max_length - 1 > ops.LOGITS_PROCESS_MAX_HIST:      # refused before decoding, not at the step that gets there
+            raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens take histories of at most "
+                             f"{ops.LOGITS_PROCESS_MAX_HIST} ids: max_length {max_length} is too long")
+        if procs is not None and do_sample and output_scores:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens together with do_sample=True and "
+                                      "output_scores=True are not supported: the differentiable scores are not processed")
         enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
         enc_mask8 = None if enc_mask is None else enc_mask.to(device=dev, dtype=torch.uint8).contiguous()
         if num_beams > 1:
@@ -282,7 +312,7 @@ class GenerationMixin:
                 on_device = self.device_beam_search and num_beams in (2, 4) and 2 * self.config.decoder.num_hidden_layers <= 16
                 search = self._beam_search_session if on_device else self._beam_search
                 seqs, seq_scores = search(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams,
-                                          bos_token_id, eos_token_id, pad_token_id, length_penalty)
+                                          bos_token_id, eos_token_id, pad_token_id, length_penalty, procs=procs, n_ret=n_ret)
             if return_dict_in_generate:
                 return ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None)
             return seqs
@@ -290,7 +320,14 @@ class GenerationMixin:
         prompt_len = ids.shape[1]
         rec = {"tt": [], "pos": []}
         margins = []
-        plain = forced_tokens is None and not return_margins and not record_inputs
+        plain = forced_tokens is None and not return_margins and not record_inputs and procs is None and n_ret == 1
+        if n_ret > 1:
+            # sampling of n sequences per study: B * n rows, sample-major (row j * B + b) over ONE copy of the encoder rows when the decode
+            # kernels can share them (2 or 4 query rows per K/V stream), else over repeated rows; returned study-major (TF5 repeat_interleave)
+            ids = ids.repeat(n_ret, 1)
+            if n_ret not in (2, 4) or forced_tokens is not None or return_margins:
+                enc16 = enc16.repeat(n_ret, 1, 1)
+                enc_mask8 = None if enc_mask8 is None else enc_mask8.repeat(n_ret, 1)
         # ---- the SCST caller's pair of decodes (reference scst/gt_prompt.py:162-180 then :94-112): a sampling call with scores, followed by a
         # greedy call over the SAME encoder outputs and prompt. A cached decode step costs the same for 16 and for 32 rows (it streams the
         # decoder weights), so the sampling call decodes the greedy rows too -- with the arguments the greedy call of the PREVIOUS step used --
@@ -319,16 +356,28 @@ class GenerationMixin:
         elif forced_tokens is None and not return_margins:
             ids = self._generate_session(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
                                          pad_token_id, do_sample, top_k, temperature, rec if ((output_scores and do_sample) or record_inputs) else None,
-                                         top_p=top_p)
+                                         top_p=top_p, procs=procs)
         else:
             ids, margins = self._generate_eager(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
                                                 pad_token_id, forced_tokens, return_margins,
-                                                rec if ((output_scores and do_sample) or record_inputs) else None)
+                                                rec if ((output_scores and do_sample) or record_inputs) else None, procs=procs)
+        order = None
+        if n_ret > 1:
+            # the decode's rows are sample-major (row j * B + b); the re-scoring pass runs over the SAME rows in the same order -- dropout masks are
+            # keyed by row, so each sampled token is scored by the forward that drew it -- over repeated encoder rows (gradient reaches enc); its
+            # scores, the sequences and the recorded inputs are then put study-major (TF5 repeat_interleave)
+            Bs = ids.shape[0] // n_ret
+            order = torch.arange(ids.shape[0], device=ids.device).view(n_ret, Bs).t().reshape(-1)
+            enc = enc.repeat(n_ret, *([1] * (enc.dim() - 1)))
+            enc_mask = None if enc_mask is None else enc_mask.repeat(n_ret, *([1] * (enc_mask.dim() - 1)))
 
         scores = None
         if output_scores and do_sample:
             scores = self._rescore_sampled(ids, prompt_len, rec, enc, enc_mask, special_token_ids, mask_token_id, bos_token_id,
-                                           top_k, temperature, top_p)
+                                           top_k, temperature, top_p, order=order)
+        if order is not None:
+            ids = ids[order]
+            rec = {k: ([None if t is None else t[order] for t in v] if k in ("tt", "pos") else v) for k, v in rec.items()}
         if return_dict_in_generate:
             out = ModelOutput(sequences=ids, scores=scores)
             if record_inputs:
@@ -340,7 +389,7 @@ class GenerationMixin:
         return ids
 
     def _generate_eager(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                        forced_tokens, return_margins, rec=None):
+                        forced_tokens, return_margins, rec=None, procs=None):
         """Eagerly launched greedy loop with per-step argmax / margin capture and optional teacher forcing (parity tests). rec: the per-step
         token-type / position inputs are recorded as _generate_session records them (a sampling call with forced_tokens then returns the processed
         scores of the FORCED ids: the reference's sampled sequence can be pushed through the grad-enabled generate body)."""
@@ -362,6 +411,8 @@ class GenerationMixin:
                     rec["seed"] = seed
                 logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                           seed=seed)
+                if procs is not None:                        # generation controls on the whole running history (BOS, prompt, generated)
+                    ops.logits_process_(logits, ids, ids.shape[1], -1 if eos_token_id is None else eos_token_id, *procs)
                 if forced_tokens is not None:
                     greedy_tok, mg = ops.select_token(logits, need_margin=True)
                     margins.append((greedy_tok, mg))
@@ -382,7 +433,7 @@ class GenerationMixin:
         return ids, margins
 
     def _generate_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                          do_sample, top_k, temperature, rec, top_p=1.0):
+                          do_sample, top_k, temperature, rec, top_p=1.0, procs=None):
         """Greedy / top-k sampling over a DecodeSession (static buffers, graph-replayed steps, EOS polled every 8 steps)."""
         dev = self.device
         B, prompt_len = ids.shape
@@ -394,7 +445,8 @@ class GenerationMixin:
                 kind, special = "pair", (tuple(special_token_ids[0]), tuple(special_token_ids[1]))
             else:
                 kind, special = ("sample" if do_sample else "greedy"), tuple(special_token_ids)
-            mode = (kind, special, mask_token_id, int(top_k or 0), float(temperature), eos_token_id, pad_token_id, bool(self.training), float(top_p))
+            mode = (kind, special, mask_token_id, int(top_k or 0), float(temperature), eos_token_id, pad_token_id, bool(self.training), float(top_p),
+                    procs)
             if rec is not None:
                 rec["seed"] = ses.seed.clone() if self.training else None
                 # the session's cross-attention K / V of every layer (valid until the session's next decode) and the weight version they belong to
@@ -501,8 +553,10 @@ class GenerationMixin:
     generate = torch.no_grad()(_generate)          # `.generate.__wrapped__` is the grad-enabled body (reference scst/gt_prompt.py:162)
 
     # ------------------------------------------------------------------------------------------ differentiable scores
-    def _rescore_sampled(self, ids, prompt_len, rec, enc, enc_mask, special_token_ids, mask_token_id, bos_token_id, top_k, temperature, top_p=1.0):
-        """Processed scores of every sampling step, [B,V] each, with autograd through the decoder (and encoder_outputs)."""
+    def _rescore_sampled(self, ids, prompt_len, rec, enc, enc_mask, special_token_ids, mask_token_id, bos_token_id, top_k, temperature, top_p=1.0,
+                         order=None):
+        """Processed scores of every sampling step, [B,V] each, with autograd through the decoder (and encoder_outputs). ids, rec and enc are in the
+        decode's row order; order: the row permutation of the returned scores (num_return_sequences: decode order -> study-major)."""
         fed = self._fed(ids, bos_token_id)
         stripped = ids.shape[1] - fed.shape[1]
         n_new = ids.shape[1] - prompt_len
@@ -539,17 +593,19 @@ class GenerationMixin:
         # the full [B, T, V] size: 85 ms per SCST step at the benchmark shape). Each step remembers where it came from so that the caller's
         # `torch.stack(scores, dim=-1)` is a view of `sc` again (modelling.BoundaryTensor).
         from .modelling import _as_boundary
-        sc = sc.contiguous()
+        sc = sc.contiguous() if order is None else sc[order]
         return tuple(_as_boundary(s_t, kind="step", base=sc, t=t) for t, s_t in enumerate(sc.unbind(1)))
 
     # ------------------------------------------------------------------------------------------ beam search
-    def _beam_search_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty):
+    def _beam_search_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
+                             procs=None, n_ret=1):
         """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False, early_stopping=False, num_return_sequences=1) over a DecodeSession:
         beams*B rows decoded by the cached-step kernels (the beams of a study share its cross-attention K/V: ONE copy of the encoder rows, as in
         the SCST sample+greedy batch), the whole per-step bookkeeping in one kernel launch (ops.beam_step), the cache reorder in another, the
         steps replayed from hipGraphs eight at a time, and the stop condition polled asynchronously every 8 steps (the stopped state is frozen
         on the device, so overshoot steps change nothing). The host loop `_beam_search` does the same with ~40 tensor ops and two
-        synchronisations per token."""
+        synchronisations per token. procs: the generation controls, applied to the log-probs (log_softmax, then csrc/logits_proc.hip, then the beam
+        step over the processed log-probs as they are). Returns the n_ret best finished hypotheses of every study, study-major, and their scores."""
         B, prompt_len = ids.shape
         nb = num_beams
         pad = 0 if pad is None else pad
@@ -559,7 +615,8 @@ class GenerationMixin:
             ses.reset(ids.repeat(nb, 1), enc16, enc_mask8)
             ses.ids[:, prompt_len:] = pad
             st = ses.beam_state(nb, pad)
-            mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length))
+            mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length),
+                    procs)
             cur = prompt_len
             poll = None
             while cur < max_length:
@@ -577,17 +634,22 @@ class GenerationMixin:
                     ev = torch.cuda.Event()
                     ev.record()
                     poll = (ses.poll_host, ev)
-            out = st["sequences"][0].clone()
-            scores = st["beam_scores"][:, 0].clone()
+            if n_ret == 1:
+                out = st["sequences"][0].clone()
+                scores = st["beam_scores"][:, 0].clone()
+            else:                                                           # the finished set is held best first: [n, B] -> study-major rows
+                out = st["sequences"][:n_ret].transpose(0, 1).reshape(B * n_ret, st["sequences"].shape[2]).clone()
+                scores = st["beam_scores"][:, :n_ret].reshape(-1).clone()
         if eos is None:
             return out, scores
         gen = out[:, prompt_len:]
         is_eos = gen == eos
-        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), gen.shape[1], device=out.device))
+        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((out.shape[0],), gen.shape[1], device=out.device))
         return out[:, : prompt_len + int(lens.max())], scores
 
-    def _beam_search(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty):
-        """TF5 generation/utils.py:3208-3560 with do_sample=False, early_stopping=False, one EOS id, num_return_sequences=1."""
+    def _beam_search(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
+                     procs=None, n_ret=1):
+        """TF5 generation/utils.py:3208-3560 with do_sample=False, early_stopping=False, one EOS id; the n_ret best hypotheses per study."""
         dev = ids.device
         B = ids.shape[0]
         nb, keep = num_beams, 2 * num_beams
@@ -620,7 +682,12 @@ class GenerationMixin:
             new, mask, tt, pos = self._step_inputs(fed, special_token_ids, mask_token_id, prefill=cache.len == 0)
             logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                       seed=seed)
-            ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
+            if procs is None:
+                ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
+            else:                                                                             # processors act on the log-probs (TF5:gen:3388-3389)
+                ops.log_softmax_rows_(logits)
+                ops.logits_process_(logits, flat.contiguous(), cur, -1 if eos is None else eos, *procs)
+                logits.add_(run_scores.view(-1, 1))
             topk_lp, topk_idx = ops.topk_rows(logits.view(B, nb * V), keep)
             beam_of = topk_idx // V
             topk_seq = gather(running, beam_of)
@@ -645,10 +712,11 @@ class GenerationMixin:
             unsat = unsat & torch.any(best_run > worst_fin, dim=-1, keepdim=True)
             if not (bool(unsat.any()) and not bool(hits.all())):
                 break
-        out = sequences[:, 0, :]
+        out = sequences[:, 0, :] if n_ret == 1 else sequences[:, :n_ret, :].reshape(B * n_ret, -1)
+        sc = beam_scores[:, 0] if n_ret == 1 else beam_scores[:, :n_ret].reshape(-1)
         if eos is None:
-            return out, beam_scores[:, 0]
+            return out, sc
         gen = out[:, prompt_len:]
         is_eos = gen == eos
-        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), gen.shape[1], device=dev))
-        return out[:, : prompt_len + int(lens.max())], beam_scores[:, 0]
+        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((out.shape[0],), gen.shape[1], device=dev))
+        return out[:, : prompt_len + int(lens.max())], sc

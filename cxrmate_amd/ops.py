@@ -1118,6 +1118,22 @@ def log_softmax_rows_(x, add_row=None):
     return x
 
 
+LOGITS_PROCESS_MAX_HIST = 512
+
+
+def logits_process_(scores, ids, cur, eos=-1, penalty=1.0, ngram=0, min_length=0):
+    """Generation controls in place on fp32 score rows [R, V] (csrc/logits_proc.hip; include/cxrmate_hip.h cxr_logits_process_f32): repetition
+    penalty, n-gram ban, EOS ban while cur < min_length, over the history ids[:, :cur] (int64 [R, >= cur], unit column stride)."""
+    R, V = scores.shape
+    assert scores.dtype == torch.float32 and scores.stride(1) == 1
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == R and ids.stride(1) == 1 and ids.shape[1] >= cur
+    if cur > LOGITS_PROCESS_MAX_HIST:
+        raise ValueError(f"generation controls take histories of at most {LOGITS_PROCESS_MAX_HIST} ids (got {cur})")
+    LIB.call("cxr_logits_process_f32", _p(scores), scores.stride(0), _p(ids), ids.stride(0), R, V, int(cur), int(eos), float(penalty), int(ngram),
+             int(min_length), _s())
+    return scores
+
+
 # ------------------------------------------------------------------------------------------------ optimiser / plumbing
 def adamw_step(p, g, m, v, p16, lr, b1, b2, eps, wd, step, gscale=1.0, step_dev=None):
     """step >= 1: host step count. step == 0 with step_dev (int32 device scalar): the kernel reads the count itself (graph replay)."""
@@ -1217,15 +1233,17 @@ def beam_ws(rows, V, nb, device):
     return torch.empty(rows * ((V + 4095) // 4096) * (2 + 4 * nb), dtype=torch.float32, device=device)
 
 
-def beam_step(logits, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, cur, max_length, eos, div, ws=None):
-    """One device-side beam-search step (csrc/decode.hip beam_scan_kernel + beam_step_kernel; include/cxrmate_hip.h cxr_beam_step). Beam-major rows."""
+def beam_step(logits, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, cur, max_length, eos, div, ws=None,
+              logprobs=False):
+    """One device-side beam-search step (csrc/decode.hip beam_scan_kernel + beam_step_kernel; include/cxrmate_hip.h cxr_beam_step). Beam-major rows.
+    logprobs=True: `logits` are log-probs already processed by the generation controls, taken as they are (cxr_beam_step_lp)."""
     nb, B, L = running.shape
     R, V = logits.shape
     assert R == nb * B and logits.dtype == torch.float32 and running.is_contiguous() and sequences.is_contiguous()
     if ws is None:
         ws = beam_ws(R, V, nb, logits.device)
     assert ws.numel() >= R * ((V + 4095) // 4096) * (2 + 4 * nb)
-    LIB.call("cxr_beam_step", _p(logits), logits.stride(0), _p(running), _p(sequences), _p(run_scores), _p(beam_scores), _p(finished), _p(unsat),
+    LIB.call("cxr_beam_step_lp" if logprobs else "cxr_beam_step", _p(logits), logits.stride(0), _p(running), _p(sequences), _p(run_scores), _p(beam_scores), _p(finished), _p(unsat),
              _p(allhit), _p(beam_idx), _p(ws), B, nb, V, L, int(cur), int(max_length), int(eos), float(div), _s())
 
 

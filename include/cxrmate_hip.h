@@ -317,6 +317,14 @@ int cxr_select_token(const float* logits, long ld, long R, int V, int mode, floa
                         the rest take the argmax in the same launch (negative n_sample = all rows) */
 int cxr_log_softmax_rows(float* x, long ld, long R, int V, const float* add_row, hipStream_t stream);
 
+/* ---- generation controls (TF5 logits_process.py: RepetitionPenalty :306, NoRepeatNGram :1021-1110, MinLength :101 / MinNewTokens :164, in
+ * the order of TF5:gen:1174-1235). In place on fp32 score rows logits [R, V] (raw logits, or log-probs on the beam path); ids int64 [R, ids_ld],
+ * history = columns [0, cur), cur <= 512. penalty 1 = off (else > 0: x < 0 ? x * penalty : x / penalty on every history id, once), ngram 0 =
+ * off (ids completing an n-gram of the history -> -inf; nothing while cur < ngram), eos -> -inf while cur < min_length (absolute length, the
+ * caller folds min_new_tokens in). One workgroup per row; capturable. */
+int cxr_logits_process_f32(float* logits, long ld, const long* ids, long ids_ld, long R, int V, int cur, long eos, float penalty, int ngram,
+                           int min_length, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3fn) linear layers of the frozen encoder (BASELINE.json configs[4]; caller REF:modules/lightning_modules/longitudinal/scst/
  * gen_prompt.py:174-259, encoder under no_grad). C[M,N] = epi(scale * A8[M,K] . W8[N,K]^T): one scale per tensor (scale = s_A * s_W), fp32
  * accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales; epi = + bias, GELU (act 1), + residual (bf16); output bf16 (C) and / or
@@ -424,6 +432,11 @@ int cxr_topk_rows(const float* x, long ld, long R, int n, int K, float* vals, lo
 int cxr_beam_step(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
                   int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur, int max_length, long eos, float div,
                   hipStream_t stream);
+/* cxr_beam_step over log-probs a caller has already normalised and processed (generation controls, TF5:gen:3388-3389): the candidate score is
+ * logprobs + running score, with no log-softmax of its own. Same state, workspace and arguments. */
+int cxr_beam_step_lp(const float* logprobs, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
+                     int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur, int max_length, long eos, float div,
+                     hipStream_t stream);
 /* out[i][r, :rows, :] = in[i][idx[r], :rows, :] for n <= 16 tensors [B, *, C] of one geometry (host arrays of device pointers): the KV-cache
  * reorder of a beam step for all layers in one launch (TF5:gen:3468-3478) */
 int cxr_gather_batch_multi_bf16(const void* const* in, void* const* out, int n, long bs, long rs, const long* idx, int B, int rows, int C,
