@@ -95,6 +95,7 @@ struct BeamArgs {
     long eos;
     float div;                             // (cur + 1 - prompt_len) ^ length_penalty
     int prenorm;                           // 1: `logits` are already (processed) log-probs, taken as they are (log-sum-exp fixed at 0)
+    int* run_bidx; int* fin_bidx;          // int32 [beams, B, L] beam-index histories (cxr_beam_step_idx only; null otherwise)
 };
 constexpr int BEAM_CHUNK = 4096;           // vocabulary entries per scan workgroup (16 per thread, held in registers)
 
@@ -163,7 +164,10 @@ __global__ __launch_bounds__(256) void beam_scan_kernel(const BeamArgs a) {
     }
 }
 
-template <int NB>
+// BIDX: the beam-index history of TF5 (_get_top_k_continuations :3116-3127, _get_running_beams_for_next_iteration :3150, _update_finished_beams
+// :3197-3202) beside the token rows: column t of a beam holds the study-major row (study * beams + beam) its token of column t was chosen from,
+// -1 where no token was chosen (prompt columns, columns after a hypothesis ended). Gathered from the parent on reorder, copied on finishing.
+template <int NB, bool BIDX>
 __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
     constexpr int K2 = 2 * NB;
     constexpr int MAXC = NB * 32 * K2;                                    // candidates: beams x chunks (<= 32) x K2
@@ -294,22 +298,46 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
             a.running[((long)i * B + b) * a.L + t] = r;
             a.sequences[((long)i * B + b) * a.L + t] = q;
         }
+        if constexpr (BIDX) {
+            int oldrb[NB], oldsb[NB];
+#pragma unroll
+            for (int g = 0; g < NB; ++g) {
+                oldrb[g] = a.run_bidx[((long)g * B + b) * a.L + t];
+                oldsb[g] = a.fin_bidx[((long)g * B + b) * a.L + t];
+            }
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                int r = -1, q = -1;
+                const int par = s_parent[i], src = s_src[i];
+                const int cb = src >= NB ? c_beam[src - NB] : 0;
+#pragma unroll
+                for (int g = 0; g < NB; ++g) {
+                    if (g == par) r = oldrb[g];
+                    if (src < NB ? g == src : g == cb) q = src < NB ? oldsb[g] : oldrb[g];
+                }
+                if (t == a.cur) { r = b * NB + par; if (src >= NB) q = b * NB + cb; }
+                a.run_bidx[((long)i * B + b) * a.L + t] = r;
+                a.fin_bidx[((long)i * B + b) * a.L + t] = q;
+            }
+        }
     }
 }
 // div = (cur + 1 - prompt_len) ** length_penalty, evaluated in double by the caller as the library evaluates the Python power, rounded to
 // fp32 as its tensor division does. ws: beams*B * ceil(V / 4096) * (2 + 4*beams) floats.
 static int beam_step_launch(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
                             unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
-                            int max_length, long eos, float div, int prenorm, hipStream_t stream) {
+                            int max_length, long eos, float div, int prenorm, int* run_bidx, int* fin_bidx, hipStream_t stream) {
     if (B <= 0 || V <= 0 || cur < 0 || cur >= L || (nb != 1 && nb != 2 && nb != 3 && nb != 4 && nb != 5 && nb != 8) || (long)nb * V >= (1L << 31) || !ws)
         return CXR_ERR_ARG;
     const int nch = cdiv(V, BEAM_CHUNK);
-    if (nch > 32) return CXR_ERR_ARG;
+    if (nch > 32 || (run_bidx == nullptr) != (fin_bidx == nullptr)) return CXR_ERR_ARG;
     BeamArgs a{logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur, max_length, cur & 1,
-               nch, eos, div, prenorm};
+               nch, eos, div, prenorm, run_bidx, fin_bidx};
     const dim3 sg(nch, nb * B);
+    const bool bidx = run_bidx != nullptr;
 #define BEAM_CASE(NB_) case NB_: CXR_LAUNCH(beam_scan_kernel<2 * NB_>, sg, dim3(256), 0, stream, a);                       \
-                                 CXR_LAUNCH(beam_step_kernel<NB_>, dim3(B), dim3(256), 0, stream, a); break
+                                 if (bidx) CXR_LAUNCH((beam_step_kernel<NB_, true>), dim3(B), dim3(256), 0, stream, a);     \
+                                 else CXR_LAUNCH((beam_step_kernel<NB_, false>), dim3(B), dim3(256), 0, stream, a); break
     switch (nb) { BEAM_CASE(1); BEAM_CASE(2); BEAM_CASE(3); BEAM_CASE(4); BEAM_CASE(5); default: BEAM_CASE(8); }
 #undef BEAM_CASE
     CXR_LAUNCH_CHECK();
@@ -319,7 +347,7 @@ extern "C" int cxr_beam_step(const float* logits, long ld, long* running, long* 
                              unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
                              int max_length, long eos, float div, hipStream_t stream) {
     return beam_step_launch(logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
-                            max_length, eos, div, 0, stream);
+                            max_length, eos, div, 0, nullptr, nullptr, stream);
 }
 // The same step over log-probs the generation controls have processed (TF5:gen:3388-3389: processors act on log_softmax(logits), nothing
 // renormalises afterwards): candidate score = logprob + running score.
@@ -327,7 +355,16 @@ extern "C" int cxr_beam_step_lp(const float* logprobs, long ld, long* running, l
                                 unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
                                 int max_length, long eos, float div, hipStream_t stream) {
     return beam_step_launch(logprobs, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
-                            max_length, eos, div, 1, stream);
+                            max_length, eos, div, 1, nullptr, nullptr, stream);
+}
+// Either step, with the beam-index histories of the running and the finished beams kept beside their token rows (int32 [beams, B, L], both -1
+// at the start of a search).
+extern "C" int cxr_beam_step_idx(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
+                                 unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int* run_bidx, int* fin_bidx, int B,
+                                 int nb, int V, int L, int cur, int max_length, long eos, float div, int logprobs, hipStream_t stream) {
+    if (!run_bidx || !fin_bidx) return CXR_ERR_ARG;
+    return beam_step_launch(logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
+                            max_length, eos, div, logprobs ? 1 : 0, run_bidx, fin_bidx, stream);
 }
 
 // The KV-cache reorder of a beam step for ALL layers in one launch: out[i][r, :rows, :] = in[i][idx[r], :rows, :] for up to 16 tensors of

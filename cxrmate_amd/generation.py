@@ -65,12 +65,14 @@ class DecodeSession:
         self.version = -1
         self.fills = 0                                     # number of reset()s = prefills: every one overwrites the cross K / V (decoder.SharedCrossKV)
         self.beam = None                                   # device-side beam-search state (beam_state)
+        self.rec_bufs = {}                                 # per-step outputs of generate (output_logits / output_scores): [Lmax, rows, V] fp32 each
         self._cache_home = (list(self.cache.k), list(self.cache.v), list(self.cache.k2), list(self.cache.v2))
 
-    def beam_state(self, nb, pad):
+    def beam_state(self, nb, pad, bidx=False):
         """State of a device-side beam search over this session's rows (BEAM-MAJOR: row = beam * studies + study, so the beams of a study
         share its cross-attention K/V): `self.ids` viewed [nb, B, Lmax] holds the running beams; finished beams, scores and the stop flags
-        live here (csrc/decode.hip beam_step_kernel)."""
+        live here (csrc/decode.hip beam_step_kernel). bidx: also the beam-index histories of the running and finished beams (int32 [nb, B, Lmax],
+        -1 = no token chosen), allocated on first use."""
         dev, B = self.ids.device, self.B // nb
         if self.beam is None or self.beam["nb"] != nb:
             self.beam = dict(nb=nb, sequences=torch.zeros((nb, B, self.Lmax), dtype=torch.int64, device=dev),
@@ -85,7 +87,22 @@ class DecodeSession:
         st["beam_scores"].fill_(-1.0e9); st["finished"].zero_()
         st["unsat"].fill_(1); st["allhit"].zero_()
         st["sequences"].copy_(self.ids.view(nb, B, self.Lmax))
+        if bidx:
+            if "run_bidx" not in st:                        # allocated once: graphs that captured them stay valid
+                st["run_bidx"] = torch.empty((nb, B, self.Lmax), dtype=torch.int32, device=dev)
+                st["fin_bidx"] = torch.empty((nb, B, self.Lmax), dtype=torch.int32, device=dev)
+            st["run_bidx"].fill_(-1); st["fin_bidx"].fill_(-1)
         return st
+
+    def record_buffers(self, logits, scores):
+        """Static slots of the per-step outputs a call asks for: [Lmax, rows, V] fp32, step column c -> slot c (a step graph bakes its slot's
+        address). Allocated on the first call that asks for them and never replaced, so graphs captured over them stay valid; calls without the
+        flags neither allocate nor touch them."""
+        V = self.model.config.decoder.vocab_size
+        for name, want in (("logits", logits), ("scores", scores)):
+            if want and name not in self.rec_bufs:
+                self.rec_bufs[name] = torch.empty((self.Lmax, self.ids.shape[0], V), dtype=torch.float32, device=self.ids.device)
+        return self.rec_bufs.get("logits") if logits else None, self.rec_bufs.get("scores") if scores else None
 
     def _swap_caches(self, n=1):
         c = self.cache
@@ -118,7 +135,8 @@ class DecodeSession:
 
     def step(self, cur, strip, mode, n=1):
         """Append tokens cur .. cur+n-1 (0-based columns of self.ids). mode = (kind, special_token_ids, mask_token_id, top_k, temperature, eos, pad,
-        train, top_p, procs); procs = (repetition penalty, n-gram size, absolute min length) of the generation controls, or None. The n cached
+        train, top_p, procs, rec); procs = (repetition penalty, n-gram size, absolute min length) of the generation controls, or None; rec =
+        (record logits, record scores, row groups nb of the study-major permutation) of output_logits / output_scores, or None. The n cached
         steps are ONE hipGraph (a replay costs ~9 us of launch overhead whatever it holds: per token at n = 1, per 8 tokens at n = 8)."""
         prefill = self.cache.len == 0
         if prefill or not self.model.graph_decode:
@@ -150,7 +168,10 @@ class DecodeSession:
 
     def _run(self, cur, strip, mode, prefill):
         m = self.model
-        kind, special, mask_token_id, top_k, temperature, eos, pad, train, top_p, procs = mode
+        kind, special, mask_token_id, top_k, temperature, eos, pad, train, top_p, procs, rec = mode
+        # per-step outputs (csrc/gen_record.hip): raw logits before any processor, scores as TF5 stores them; slot `cur` of the session's buffers
+        lo, so = self.record_buffers(rec[0], rec[1]) if rec is not None else (None, None)
+        lo, so = None if lo is None else lo[cur], None if so is None else so[cur]
         if prefill:
             fed = self.ids[:, strip:cur]
             new, mask, tt, pos = m._step_inputs(fed, special, mask_token_id, prefill=True)
@@ -179,12 +200,19 @@ class DecodeSession:
         if kind == "beam":                                          # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
             nb, penalty, (prompt_len, max_length) = top_k, temperature, top_p
             st, c = self.beam, self.cache
+            if procs is None and (lo is not None or so is not None):  # scores = log_softmax(logits) (TF5:gen:3387, :3396), study-major rows
+                ops.gen_record(logits, lo, so, log_softmax=True, nb=nb)
             if procs is not None:                                   # TF5 processes log_softmax(logits) on the beam path (utils.py:3388-3389)
+                if lo is not None:
+                    ops.gen_record(logits, lo, nb=nb)
                 ops.log_softmax_rows_(logits)
                 ops.logits_process_(logits, self.ids, cur, -1 if eos is None else eos, *procs)
+                if so is not None:
+                    ops.gen_record(logits, None, so, nb=nb)
             ops.beam_step(logits, self.ids.view(nb, self.B // nb, self.Lmax), st["sequences"], st["run_scores"], st["beam_scores"], st["finished"],
                           st["unsat"], st["allhit"], st["beam_idx"], cur, max_length, -1 if eos is None else eos,
-                          float(cur + 1 - prompt_len) ** penalty, ws=st["ws"], logprobs=procs is not None)
+                          float(cur + 1 - prompt_len) ** penalty, ws=st["ws"], logprobs=procs is not None,
+                          bidx=(st["run_bidx"], st["fin_bidx"]) if rec is not None else None)
             ops.gather_batch_multi(c.k + c.v, st["beam_idx"], c.len, c.k2 + c.v2)
             self._swap_caches()
             self.last_tt = self.last_pos = None
@@ -193,8 +221,15 @@ class DecodeSession:
         eos_ = eos if eos is not None else -1
         n_smp = {"greedy": 0, "sample": self.B, "pair": self.B // 2}[kind]      # rows [0, n_smp) sample, the rest take the argmax
         col = self.ids[:, cur]                                                  # the selection kernels write straight into the id buffer
+        nperm = rec[2] if rec is not None else 1
+        if procs is None and (lo is not None or so is not None):
+            ops.gen_record(logits, lo, so, nb=nperm)
         if procs is not None:                                                   # processors before the warpers of select_token (TF5 order)
+            if lo is not None:
+                ops.gen_record(logits, lo, nb=nperm)
             ops.logits_process_(logits, self.ids, cur, eos_, *procs)
+            if so is not None:
+                ops.gen_record(logits, None, so, nb=nperm)
         if n_smp:                                                               # one launch for sampled + greedy rows
             u = self.u_all[cur, :n_smp]
             ops.select_token(logits, mode=1, temperature=temperature, top_k=top_k or 0, u=u, unfinished=unf, eos=eos_, pad=pad or 0, out=col,
@@ -249,7 +284,7 @@ class GenerationMixin:
                   eos_token_id=None, pad_token_id=None, num_beams=1, do_sample=False, top_k=50, top_p=1.0, temperature=1.0,
                   output_scores=False, return_dict_in_generate=False, use_cache=True, length_penalty=1.0, return_margins=False,
                   forced_tokens=None, record_inputs=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=None,
-                  num_return_sequences=1, **unused):
+                  num_return_sequences=1, output_logits=False, **unused):
         from .modelling import ModelOutput
         if inputs is not None and pixel_values is None:
             pixel_values = inputs
@@ -304,6 +339,9 @@ class GenerationMixin:
                                       "output_scores=True are not supported: the differentiable scores are not processed")
         enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
         enc_mask8 = None if enc_mask is None else enc_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        # per-step outputs (TF5 GenerateOutput fields): recorded only when the dict output asks for them
+        want_logits = bool(output_logits) and bool(return_dict_in_generate)
+        want_scores = bool(output_scores) and bool(return_dict_in_generate)
         if num_beams > 1:
             if do_sample:
                 raise NotImplementedError("beam sampling is not used by the reference")
@@ -311,16 +349,30 @@ class GenerationMixin:
                 # device-side search: beam counts with a shared-K/V attention kernel, and a cache the one-launch reorder can address (16 tensors = 8 layers)
                 on_device = self.device_beam_search and num_beams in (2, 4) and 2 * self.config.decoder.num_hidden_layers <= 16
                 search = self._beam_search_session if on_device else self._beam_search
+                record = (want_logits, want_scores) if (want_logits or want_scores) else None
+                rec_out = {}
                 seqs, seq_scores = search(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams,
-                                          bos_token_id, eos_token_id, pad_token_id, length_penalty, procs=procs, n_ret=n_ret)
+                                          bos_token_id, eos_token_id, pad_token_id, length_penalty, procs=procs, n_ret=n_ret,
+                                          record=record, rec_out=rec_out)
             if return_dict_in_generate:
-                return ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None)
+                out = ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None)
+                if want_scores:                                     # TF5 GenerateBeamEncoderDecoderOutput field order
+                    out["scores"] = rec_out["scores"]
+                if want_logits:
+                    out["logits"] = rec_out["logits"]
+                if record is not None:
+                    out["beam_indices"] = rec_out["beam_indices"]
+                return out
             return seqs
 
         prompt_len = ids.shape[1]
         rec = {"tt": [], "pos": []}
         margins = []
-        plain = forced_tokens is None and not return_margins and not record_inputs and procs is None and n_ret == 1
+        # greedy scores and every call's logits are recorded per step: never served by / decoded along the SCST speculative greedy pass
+        rec_logits, rec_scores = want_logits, want_scores and not do_sample
+        record = (rec_logits, rec_scores, n_ret) if (rec_logits or rec_scores) else None
+        rec_out = {}
+        plain = forced_tokens is None and not return_margins and not record_inputs and procs is None and n_ret == 1 and record is None
         if n_ret > 1:
             # sampling of n sequences per study: B * n rows, sample-major (row j * B + b) over ONE copy of the encoder rows when the decode
             # kernels can share them (2 or 4 query rows per K/V stream), else over repeated rows; returned study-major (TF5 repeat_interleave)
@@ -356,11 +408,12 @@ class GenerationMixin:
         elif forced_tokens is None and not return_margins:
             ids = self._generate_session(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
                                          pad_token_id, do_sample, top_k, temperature, rec if ((output_scores and do_sample) or record_inputs) else None,
-                                         top_p=top_p, procs=procs)
+                                         top_p=top_p, procs=procs, record=record, rec_out=rec_out)
         else:
             ids, margins = self._generate_eager(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
                                                 pad_token_id, forced_tokens, return_margins,
-                                                rec if ((output_scores and do_sample) or record_inputs) else None, procs=procs)
+                                                rec if ((output_scores and do_sample) or record_inputs) else None, procs=procs, record=record,
+                                                rec_out=rec_out)
         order = None
         if n_ret > 1:
             # the decode's rows are sample-major (row j * B + b); the re-scoring pass runs over the SAME rows in the same order -- dropout masks are
@@ -371,7 +424,7 @@ class GenerationMixin:
             enc = enc.repeat(n_ret, *([1] * (enc.dim() - 1)))
             enc_mask = None if enc_mask is None else enc_mask.repeat(n_ret, *([1] * (enc_mask.dim() - 1)))
 
-        scores = None
+        scores = rec_out.get("scores")
         if output_scores and do_sample:
             scores = self._rescore_sampled(ids, prompt_len, rec, enc, enc_mask, special_token_ids, mask_token_id, bos_token_id,
                                            top_k, temperature, top_p, order=order)
@@ -380,6 +433,8 @@ class GenerationMixin:
             rec = {k: ([None if t is None else t[order] for t in v] if k in ("tt", "pos") else v) for k, v in rec.items()}
         if return_dict_in_generate:
             out = ModelOutput(sequences=ids, scores=scores)
+            if rec_logits:
+                out["logits"] = rec_out["logits"]
             if record_inputs:
                 out["recorded_inputs"] = rec
             if margins:
@@ -389,14 +444,16 @@ class GenerationMixin:
         return ids
 
     def _generate_eager(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                        forced_tokens, return_margins, rec=None, procs=None):
+                        forced_tokens, return_margins, rec=None, procs=None, record=None, rec_out=None):
         """Eagerly launched greedy loop with per-step argmax / margin capture and optional teacher forcing (parity tests). rec: the per-step
         token-type / position inputs are recorded as _generate_session records them (a sampling call with forced_tokens then returns the processed
-        scores of the FORCED ids: the reference's sampled sequence can be pushed through the grad-enabled generate body)."""
+        scores of the FORCED ids: the reference's sampled sequence can be pushed through the grad-enabled generate body). record / rec_out: the
+        per-step logits / processed scores, as _generate_session records them."""
         dev = self.device
         B = ids.shape[0]
         prompt_len = ids.shape[1]
         margins = []
+        got = {"logits": [], "scores": []}
         with torch.no_grad():
             cache = self._dec.new_cache(B, max_length, dev)
             unfinished = torch.ones(B, dtype=torch.int32, device=dev)
@@ -411,8 +468,12 @@ class GenerationMixin:
                     rec["seed"] = seed
                 logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                           seed=seed)
+                if record is not None and record[0]:
+                    got["logits"].append(ops.gen_record(logits, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[0])
                 if procs is not None:                        # generation controls on the whole running history (BOS, prompt, generated)
                     ops.logits_process_(logits, ids, ids.shape[1], -1 if eos_token_id is None else eos_token_id, *procs)
+                if record is not None and record[1]:
+                    got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[1])
                 if forced_tokens is not None:
                     greedy_tok, mg = ops.select_token(logits, need_margin=True)
                     margins.append((greedy_tok, mg))
@@ -430,23 +491,31 @@ class GenerationMixin:
                     break
                 if eos_token_id is not None and forced_tokens is None and int(unfinished.max()) == 0:
                     break
+        if rec_out is not None and record is not None:
+            for k, want in zip(("logits", "scores"), record[:2]):
+                if want:
+                    rec_out[k] = tuple(got[k])
         return ids, margins
 
     def _generate_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                          do_sample, top_k, temperature, rec, top_p=1.0, procs=None):
-        """Greedy / top-k sampling over a DecodeSession (static buffers, graph-replayed steps, EOS polled every 8 steps)."""
+                          do_sample, top_k, temperature, rec, top_p=1.0, procs=None, record=None, rec_out=None):
+        """Greedy / top-k sampling over a DecodeSession (static buffers, graph-replayed steps, EOS polled every 8 steps). record = (logits, scores,
+        nb): the per-step raw logits / processed scores are recorded into the session's slots, rows put study-major over nb row groups, and handed
+        out in rec_out as one tuple of [rows, V] tensors per returned step."""
         dev = self.device
         B, prompt_len = ids.shape
         strip = 1 if (self.kind == "longitudinal" and bool(torch.all(ids[:, 0] == bos_token_id))) else 0
         with torch.no_grad():
             ses = self._session(B, enc16.shape[1], max_length, enc_mask8 is not None, share=B // enc16.shape[0])
             ses.reset(ids, enc16, enc_mask8)
+            if record is not None:                                   # before any step graph is captured (never from inside a capture)
+                ses.record_buffers(record[0], record[1])
             if do_sample == "pair":
                 kind, special = "pair", (tuple(special_token_ids[0]), tuple(special_token_ids[1]))
             else:
                 kind, special = ("sample" if do_sample else "greedy"), tuple(special_token_ids)
             mode = (kind, special, mask_token_id, int(top_k or 0), float(temperature), eos_token_id, pad_token_id, bool(self.training), float(top_p),
-                    procs)
+                    procs, record)
             if rec is not None:
                 rec["seed"] = ses.seed.clone() if self.training else None
                 # the session's cross-attention K / V of every layer (valid until the session's next decode) and the weight version they belong to
@@ -492,7 +561,15 @@ class GenerationMixin:
                 is_eos = gen == eos_token_id
                 first = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), gen.shape[1], device=dev))
                 out = out[:, : prompt_len + int(first.max())]
+            if record is not None:                                   # one copy of the returned steps (the session is reused by the next call)
+                self._copy_records(ses, record, prompt_len, out.shape[1] - prompt_len, rec_out)
         return out
+
+    @staticmethod
+    def _copy_records(ses, record, first, steps, rec_out):
+        for name, buf in zip(("logits", "scores"), ses.record_buffers(record[0], record[1])):
+            if buf is not None:
+                rec_out[name] = buf[first:first + steps].clone().unbind(0)
 
     @torch.no_grad()
     def _weights_stamp(self):
@@ -552,6 +629,25 @@ class GenerationMixin:
 
     generate = torch.no_grad()(_generate)          # `.generate.__wrapped__` is the grad-enabled body (reference scst/gt_prompt.py:162)
 
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
+        """Score of every generated token (TF5 GenerationMixin.compute_transition_scores, generation/utils.py:1433): -> [rows, steps] with
+        out[n, j] = scores[j][beam_indices[n, j], sequences[n, -steps + j]], 0 where beam_indices < 0 (a hypothesis that had ended). Without
+        beam_indices row n of every step belongs to sequence n (greedy / sampling). normalize_logits: log_softmax over the vocabulary first.
+        steps = the longest history in beam_indices (len(scores) without them); the tokens are the last `steps` columns of `sequences`."""
+        stacked = torch.stack(tuple(scores), 0)                                      # [T, R, V]
+        T, _, V = stacked.shape
+        if normalize_logits:
+            stacked = torch.log_softmax(stacked, dim=-1)
+        if beam_indices is None:
+            beam_indices = torch.arange(stacked.shape[1], device=sequences.device).view(-1, 1).expand(-1, T)
+        ended = beam_indices < 0
+        steps = int((~ended).sum(-1).max())
+        rows = beam_indices[:, :steps].long().masked_fill(ended[:, :steps], 0).to(stacked.device)
+        toks = sequences[:, sequences.shape[-1] - steps:].to(stacked.device)
+        flat = stacked[:steps].reshape(steps, -1)                                   # [steps, R * V]
+        out = flat.gather(1, (rows * V + toks).t()).t()
+        return out.masked_fill(ended[:, :steps].to(out.device), 0.0)
+
     # ------------------------------------------------------------------------------------------ differentiable scores
     def _rescore_sampled(self, ids, prompt_len, rec, enc, enc_mask, special_token_ids, mask_token_id, bos_token_id, top_k, temperature, top_p=1.0,
                          order=None):
@@ -598,14 +694,16 @@ class GenerationMixin:
 
     # ------------------------------------------------------------------------------------------ beam search
     def _beam_search_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                             procs=None, n_ret=1):
+                             procs=None, n_ret=1, record=None, rec_out=None):
         """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False, early_stopping=False, num_return_sequences=1) over a DecodeSession:
         beams*B rows decoded by the cached-step kernels (the beams of a study share its cross-attention K/V: ONE copy of the encoder rows, as in
         the SCST sample+greedy batch), the whole per-step bookkeeping in one kernel launch (ops.beam_step), the cache reorder in another, the
         steps replayed from hipGraphs eight at a time, and the stop condition polled asynchronously every 8 steps (the stopped state is frozen
         on the device, so overshoot steps change nothing). The host loop `_beam_search` does the same with ~40 tensor ops and two
         synchronisations per token. procs: the generation controls, applied to the log-probs (log_softmax, then csrc/logits_proc.hip, then the beam
-        step over the processed log-probs as they are). Returns the n_ret best finished hypotheses of every study, study-major, and their scores."""
+        step over the processed log-probs as they are). Returns the n_ret best finished hypotheses of every study, study-major, and their scores.
+        record = (logits, scores): rec_out receives the per-step raw logits / processed log-probs of the steps the search ran ([B * nb, V] each,
+        study-major) and the beam indices of the returned hypotheses (int32 [B * n_ret, generated length]), as TF5 returns them."""
         B, prompt_len = ids.shape
         nb = num_beams
         pad = 0 if pad is None else pad
@@ -614,9 +712,11 @@ class GenerationMixin:
             ses = self._session(B * nb, enc16.shape[1], max_length, enc_mask8 is not None, share=nb)
             ses.reset(ids.repeat(nb, 1), enc16, enc_mask8)
             ses.ids[:, prompt_len:] = pad
-            st = ses.beam_state(nb, pad)
+            st = ses.beam_state(nb, pad, bidx=record is not None)
+            if record is not None:                                   # before any step graph is captured (never from inside a capture)
+                ses.record_buffers(record[0], record[1])
             mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length),
-                    procs)
+                    procs, None if record is None else (record[0], record[1], nb))
             cur = prompt_len
             poll = None
             while cur < max_length:
@@ -640,6 +740,12 @@ class GenerationMixin:
             else:                                                           # the finished set is held best first: [n, B] -> study-major rows
                 out = st["sequences"][:n_ret].transpose(0, 1).reshape(B * n_ret, st["sequences"].shape[2]).clone()
                 scores = st["beam_scores"][:, :n_ret].reshape(-1).clone()
+            if record is not None:
+                # steps the search ran (later launches are frozen): every running beam has a parent in each of their columns
+                steps = int((st["run_bidx"][0, 0, prompt_len:] >= 0).sum())
+                self._copy_records(ses, (record[0], record[1]), prompt_len, steps, rec_out)
+                bidx = st["fin_bidx"][:n_ret].transpose(0, 1).reshape(B * n_ret, -1)[:, prompt_len:]
+                rec_out["beam_indices"] = self._trim_beam_indices(bidx)
         if eos is None:
             return out, scores
         gen = out[:, prompt_len:]
@@ -647,9 +753,15 @@ class GenerationMixin:
         lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((out.shape[0],), gen.shape[1], device=out.device))
         return out[:, : prompt_len + int(lens.max())], scores
 
+    @staticmethod
+    def _trim_beam_indices(bidx):
+        """TF5:gen:3517-3523: the history columns up to the longest returned hypothesis."""
+        return bidx[:, :int((bidx >= 0).sum(1).max())].clone()
+
     def _beam_search(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                     procs=None, n_ret=1):
-        """TF5 generation/utils.py:3208-3560 with do_sample=False, early_stopping=False, one EOS id; the n_ret best hypotheses per study."""
+                     procs=None, n_ret=1, record=None, rec_out=None):
+        """TF5 generation/utils.py:3208-3560 with do_sample=False, early_stopping=False, one EOS id; the n_ret best hypotheses per study.
+        record / rec_out as in _beam_search_session, with the beam-index histories kept by torch ops."""
         dev = ids.device
         B = ids.shape[0]
         nb, keep = num_beams, 2 * num_beams
@@ -670,6 +782,10 @@ class GenerationMixin:
         batch_off = (torch.arange(B, device=dev) * nb).view(B, 1)
         cache = self._dec.new_cache(B * nb, max_length, dev)
         seed = self.next_dropout_seed() if self.training else None
+        if record is not None:                                     # beam-index histories (TF5:gen:3348-3351), absolute token columns
+            run_bidx = torch.full((B, nb, max_length), -1, dtype=torch.int32, device=dev)
+            fin_bidx = run_bidx.clone()
+            got = {"logits": [], "scores": []}
 
         def gather(t, idx):
             while idx.dim() < t.dim():
@@ -682,11 +798,20 @@ class GenerationMixin:
             new, mask, tt, pos = self._step_inputs(fed, special_token_ids, mask_token_id, prefill=cache.len == 0)
             logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                       seed=seed)
+            if record is not None and (record[0] or procs is None):           # raw logits; without processors the log-probs in the same pass
+                lo = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if record[0] else None
+                so = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if record[1] and procs is None else None
+                ops.gen_record(logits, lo, so, log_softmax=True)
+                for k, t in (("logits", lo), ("scores", so)):
+                    if t is not None:
+                        got[k].append(t)
             if procs is None:
                 ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
             else:                                                                             # processors act on the log-probs (TF5:gen:3388-3389)
                 ops.log_softmax_rows_(logits)
                 ops.logits_process_(logits, flat.contiguous(), cur, -1 if eos is None else eos, *procs)
+                if record is not None and record[1]:
+                    got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device))[1])
                 logits.add_(run_scores.view(-1, 1))
             topk_lp, topk_idx = ops.topk_rows(logits.view(B, nb * V), keep)
             beam_of = topk_idx // V
@@ -697,6 +822,10 @@ class GenerationMixin:
             nxt = torch.topk(run_lp, k=nb)[1]
             running, run_scores = gather(topk_seq, nxt), gather(run_lp, nxt)
             beam_idx = (gather(beam_of, nxt) + batch_off).view(-1)
+            if record is not None:                                  # TF5:gen:3116-3127, :3150
+                topk_bidx = gather(run_bidx, beam_of)
+                topk_bidx[:, :, cur] = (beam_of + batch_off).to(torch.int32)
+                run_bidx = gather(topk_bidx, nxt)
             just = hits & top_mask[None, :]
             fin_lp = topk_lp / ((cur + 1 - prompt_len) ** length_penalty)
             fin_lp = fin_lp + (~unsat).float() * -1.0e9 + (~just).float() * -1.0e9
@@ -705,6 +834,8 @@ class GenerationMixin:
             m_fin = torch.cat((finished, just), dim=1)
             best = torch.topk(m_sc, k=nb)[1]
             sequences, beam_scores, finished = gather(m_seq, best), gather(m_sc, best), gather(m_fin, best)
+            if record is not None:                                  # TF5:gen:3197-3202
+                fin_bidx = gather(torch.cat((fin_bidx, topk_bidx), dim=1), best)
             cache.reorder(beam_idx.contiguous())
             cur += 1
             best_run = run_scores[:, :1] / ((cur - prompt_len) ** length_penalty)
@@ -714,6 +845,11 @@ class GenerationMixin:
                 break
         out = sequences[:, 0, :] if n_ret == 1 else sequences[:, :n_ret, :].reshape(B * n_ret, -1)
         sc = beam_scores[:, 0] if n_ret == 1 else beam_scores[:, :n_ret].reshape(-1)
+        if record is not None:
+            for k, want in zip(("logits", "scores"), record):
+                if want:
+                    rec_out[k] = tuple(got[k])
+            rec_out["beam_indices"] = self._trim_beam_indices(fin_bidx[:, :n_ret, prompt_len:].reshape(B * n_ret, -1))
         if eos is None:
             return out, sc
         gen = out[:, prompt_len:]

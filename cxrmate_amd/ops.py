@@ -1234,17 +1234,37 @@ def beam_ws(rows, V, nb, device):
 
 
 def beam_step(logits, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, cur, max_length, eos, div, ws=None,
-              logprobs=False):
+              logprobs=False, bidx=None):
     """One device-side beam-search step (csrc/decode.hip beam_scan_kernel + beam_step_kernel; include/cxrmate_hip.h cxr_beam_step). Beam-major rows.
-    logprobs=True: `logits` are log-probs already processed by the generation controls, taken as they are (cxr_beam_step_lp)."""
+    logprobs=True: `logits` are log-probs already processed by the generation controls, taken as they are (cxr_beam_step_lp).
+    bidx=(run_bidx, fin_bidx): int32 [nb, B, L] beam-index histories of the running and finished beams, kept in the same launch (cxr_beam_step_idx)."""
     nb, B, L = running.shape
     R, V = logits.shape
     assert R == nb * B and logits.dtype == torch.float32 and running.is_contiguous() and sequences.is_contiguous()
     if ws is None:
         ws = beam_ws(R, V, nb, logits.device)
     assert ws.numel() >= R * ((V + 4095) // 4096) * (2 + 4 * nb)
+    if bidx is not None:
+        for t in bidx:
+            assert t.dtype == torch.int32 and t.shape == (nb, B, L) and t.is_contiguous(), (t.dtype, t.shape)
+        LIB.call("cxr_beam_step_idx", _p(logits), logits.stride(0), _p(running), _p(sequences), _p(run_scores), _p(beam_scores), _p(finished),
+                 _p(unsat), _p(allhit), _p(beam_idx), _p(ws), _p(bidx[0]), _p(bidx[1]), B, nb, V, L, int(cur), int(max_length), int(eos), float(div),
+                 int(bool(logprobs)), _s())
+        return
     LIB.call("cxr_beam_step_lp" if logprobs else "cxr_beam_step", _p(logits), logits.stride(0), _p(running), _p(sequences), _p(run_scores), _p(beam_scores), _p(finished), _p(unsat),
              _p(allhit), _p(beam_idx), _p(ws), B, nb, V, L, int(cur), int(max_length), int(eos), float(div), _s())
+
+
+def gen_record(x, logits_out=None, scores_out=None, log_softmax=False, nb=1):
+    """Per-step outputs of generate in one pass over fp32 score rows x [R, V] (csrc/gen_record.hip; include/cxrmate_hip.h cxr_gen_record_f32):
+    logits_out <- x, scores_out <- x or log_softmax(x). Outputs are contiguous [R, V]; input row beam * (R // nb) + study goes to output row
+    study * nb + beam (nb = 1: the same order)."""
+    R, V = x.shape
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and R % nb == 0
+    for t in (logits_out, scores_out):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (R, V) and t.is_contiguous())
+    LIB.call("cxr_gen_record_f32", _p(x), x.stride(0), R, V, int(nb), _p(logits_out), _p(scores_out), int(bool(log_softmax)), _s())
+    return logits_out, scores_out
 
 
 def topk_rows(x, k):

@@ -325,6 +325,12 @@ int cxr_log_softmax_rows(float* x, long ld, long R, int V, const float* add_row,
 int cxr_logits_process_f32(float* logits, long ld, const long* ids, long ids_ld, long R, int V, int cur, long eos, float penalty, int ngram,
                            int min_length, hipStream_t stream);
 
+/* ---- per-step outputs of generate (TF5:gen:2902-2904 _sample, :3393-3396 _beam_search: output_logits / output_scores). One pass over the fp32 score
+ * rows x [R, V] (row stride ld) of a decode step: logits_out (optional) <- the rows as they are; scores_out (optional) <- the rows as they are, or
+ * their log_softmax when log_softmax != 0 (-inf entries stay -inf). Both outputs are contiguous [R, V], input row r (beam-major, r = beam * S +
+ * study, S = R / nb) written to output row study * nb + beam (nb = 1: the same order). One workgroup per row; capturable. */
+int cxr_gen_record_f32(const float* x, long ld, long R, int V, int nb, float* logits_out, float* scores_out, int log_softmax, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3fn) linear layers of the frozen encoder (BASELINE.json configs[4]; caller REF:modules/lightning_modules/longitudinal/scst/
  * gen_prompt.py:174-259, encoder under no_grad). C[M,N] = epi(scale * A8[M,K] . W8[N,K]^T): one scale per tensor (scale = s_A * s_W), fp32
  * accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales; epi = + bias, GELU (act 1), + residual (bf16); output bf16 (C) and / or
@@ -437,6 +443,13 @@ int cxr_beam_step(const float* logits, long ld, long* running, long* sequences, 
 int cxr_beam_step_lp(const float* logprobs, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
                      int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur, int max_length, long eos, float div,
                      hipStream_t stream);
+/* cxr_beam_step (logprobs = 0) or cxr_beam_step_lp (logprobs = 1) that also keeps the beam-index histories of TF5 (GenerateBeamOutput.beam_indices):
+ * run_bidx / fin_bidx int32 [beams,B,L] of the running / finished beams, -1 at the start of a search. Column t holds the study-major row
+ * (study * beams + beam) the token of column t was chosen from, -1 where none was (prompt columns, columns after a hypothesis ended); gathered
+ * from the parent beam on reorder, copied into the finished set with the hypothesis. Tokens, scores and flags are those of the plain step. */
+int cxr_beam_step_idx(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
+                      int* unsat, int* allhit, long* beam_idx, float* ws, int* run_bidx, int* fin_bidx, int B, int nb, int V, int L, int cur,
+                      int max_length, long eos, float div, int logprobs, hipStream_t stream);
 /* out[i][r, :rows, :] = in[i][idx[r], :rows, :] for n <= 16 tensors [B, *, C] of one geometry (host arrays of device pointers): the KV-cache
  * reorder of a beam step for all layers in one launch (TF5:gen:3468-3478) */
 int cxr_gather_batch_multi_bf16(const void* const* in, void* const* out, int n, long bs, long rs, const long* idx, int B, int rows, int C,
