@@ -98,25 +98,29 @@ __device__ __forceinline__ uint2 pack8_fp8(const float (&f)[8], float inv) {
 }
 
 // GELU(x) = x * Phi(x) with Phi(x) ~= sigmoid(x * (a1 + a3 x^2 + a5 x^4)), minimax-fitted to the exact (erf) GELU that torch.nn.GELU() /
-// ACT2FN["gelu"] compute: max |error| 2.5e-5 on the value and 1.1e-4 on the derivative (the derivative below is the exact derivative
-// of this function, so forward and backward stay consistent). 9 instructions (one v_exp, one v_rcp) instead of ~40 for libm erff: the
-// FFN GEMMs of this model have K = 384/768, i.e. only 6-12 MFMA steps to hide the epilogue of 64 outputs per lane behind.
-// The odd polynomial is evaluated on clamp(x, +-8) (it turns around beyond |x| ~ 8.3, where Phi is 0/1 to fp32 precision anyway).
+// ACT2FN["gelu"] compute. Max |error| over every finite x: 2.52e-5 on the value and 1.099e-4 on the derivative for the formula in float64
+// (tests/test_gelu_approx.py), 2.53e-5 and 1.099e-4 as the kernels evaluate it in fp32 (tests/test_kernels_gpu.py). Inside |x| <= 8 the
+// derivative below is the exact derivative of this function, so forward and backward stay consistent. 9 instructions (one v_exp, one v_rcp)
+// instead of ~40 for libm erff: the FFN GEMMs of this model have K = 384/768, i.e. only 6-12 MFMA steps to hide the epilogue of 64 outputs
+// per lane behind.
+// The polynomial is evaluated on xc = clamp(x, +-8) (it turns around beyond |x| ~ 8.3) but multiplies the unclamped x, so that Phi keeps
+// falling to exactly 0 below -8. (With xc there, Phi stayed at sigmoid(-27.6) = 1e-12 and GELU(x) = 1e-12 x reached -3.4e26 at the bottom
+// of the bf16 range.) The derivative's x (1 - s) term takes xc for the same reason: with x it overflowed to -inf for x below -2.4e38.
 #define CXR_GELU_A1 1.595015769f
 #define CXR_GELU_A3 0.07401129203f
 #define CXR_GELU_A5 (-0.0007030335804f)
-__device__ __forceinline__ float gelu_sigmoid(float x, float& x2) {
-    const float xc = __builtin_amdgcn_fmed3f(x, -8.0f, 8.0f);
+__device__ __forceinline__ float gelu_sigmoid(float x, float& xc, float& x2) {
+    xc = __builtin_amdgcn_fmed3f(x, -8.0f, 8.0f);
     x2 = xc * xc;
     const float t = fmaf(x2, fmaf(x2, CXR_GELU_A5 * -1.4426950408889634f, CXR_GELU_A3 * -1.4426950408889634f), CXR_GELU_A1 * -1.4426950408889634f);
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(xc * t));
+    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * t));           // exp2 -> +inf below x ~ -37: s = 0
 }
-__device__ __forceinline__ float gelu_f(float x) { float x2; return x * gelu_sigmoid(x, x2); }
+__device__ __forceinline__ float gelu_f(float x) { float xc, x2; return x * gelu_sigmoid(x, xc, x2); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
-    float x2;
-    const float s = gelu_sigmoid(x, x2);
+    float xc, x2;
+    const float s = gelu_sigmoid(x, xc, x2);
     const float dp = fmaf(x2, fmaf(x2, 5.0f * CXR_GELU_A5, 3.0f * CXR_GELU_A3), CXR_GELU_A1);
-    return s * fmaf(x * (1.0f - s), dp, 1.0f);
+    return s * fmaf(xc * (1.0f - s), dp, 1.0f);
 }
 
 // ---- counter-based dropout: every kernel that applies (or re-applies, in backward / in the teacher-forced re-scoring of a sampled sequence)

@@ -341,6 +341,7 @@ __global__ void bcast_row_kernel(const float* __restrict__ row, bf16_t* __restri
     out[(i / C) * out_bs + (i % C)] = f2bf(row[i % C]);
 }
 extern "C" int cxr_bcast_row_f32_bf16(const float* row, void* out, long out_bs, int B, int C, hipStream_t stream) {
+    if (B <= 0 || C <= 0) return CXR_ERR_ARG;
     CXR_LAUNCH(bcast_row_kernel, dim3(cdiv((long)B * C, 256)), dim3(256), 0, stream, row, (bf16_t*)out, out_bs, B, C);
     CXR_LAUNCH_CHECK();
     return CXR_OK;
@@ -353,6 +354,7 @@ __global__ void sum_row0_kernel(const bf16_t* __restrict__ in, long in_bs, float
     out[c] += s;
 }
 extern "C" int cxr_sum_row0_bf16_f32(const void* in, long in_bs, float* out, int B, int C, hipStream_t stream) {
+    if (B <= 0 || C <= 0) return CXR_ERR_ARG;
     CXR_LAUNCH(sum_row0_kernel, dim3(cdiv(C, 128)), dim3(128), 0, stream, (const bf16_t*)in, in_bs, out, B, C);
     CXR_LAUNCH_CHECK();
     return CXR_OK;

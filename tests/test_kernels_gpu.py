@@ -5,6 +5,7 @@ import math
 import numpy as np
 import pytest
 import torch
+from bounds_util import Guarded, all_bf16, assert_bf16_bracket, assert_f32_bound, gelu64
 
 pytestmark = pytest.mark.gpu
 
@@ -1939,3 +1940,122 @@ def test_attention_cross_mfma_with_the_query_projection_inside(ops, Bkv, share, 
     two2 = ops.attention_cross_mfma(q2, pk, Bkv, Tk, H, 0.125, kpm_bits=bits, drop=dr)
     one2 = ops.attention_cross_mfma_q(y, B, yst, 1e-12, wf, bcf, pk, Bkv, Tk, H, 0.125, kpm_bits=bits, drop=dr, out_dal=False)
     close(one2, two2, rtol=1e-2, atol=2e-2, what="fused query projection, multi-tile statistics")
+
+
+# ------------------------------------------------------------------------------------------------ GELU epilogues, exhaustively over bf16
+# Every epilogue evaluates csrc/common.h's minimax GELU. A selection weight W[n, k] = (k == n % K) makes A @ W^T exact in fp32, so with act = 1
+# output column n is gelu(A[:, n % K]) and A holds every finite bf16 value; with act = 2, A = ones and aux holds every finite bf16 value, so the
+# output is gelu'(aux). Bounds against the float64 erf GELU: fp32 outputs within 2.6e-5 (value) / 1.1e-4 (derivative) + 4 ulp_f32(ref); bf16
+# outputs between the bf16 values just outside ref -+ the same tolerance.
+GELU_TOL, GELU_D_TOL = 2.6e-5, 1.1e-4
+_N_BF16 = 65024                                                     # finite bf16 values
+
+
+def _all_bf16_filling(M, K):
+    x = all_bf16()
+    return x.repeat(-(-(M * K) // x.numel()))[:M * K].view(M, K)
+
+
+def _selection_weight(N, K):
+    w = torch.zeros(N, K)
+    w[torch.arange(N), torch.arange(N) % K] = 1
+    return w.to(BF)
+
+
+def _check_gelu(out, x, deriv, what):
+    v, d = gelu64(x.double())
+    tol = GELU_D_TOL if deriv else GELU_TOL
+    if out.dtype == torch.float32:
+        err = assert_f32_bound(out, d if deriv else v, tol, 4, what)
+        print(f"MEASURED {what}: max |err| {err:.4e}")
+    else:
+        err = assert_bf16_bracket(out, d if deriv else v, tol, what)
+        print(f"MEASURED {what}: max |err| / bracket half-width {err:.3f}")
+
+
+# name -> (route, K, N, row stride of the output / aux buffers, M); the tiled kernel's epilogue form each case reaches is in the comment
+_GELU_FORMS = {
+    "tiled": ("tiled", 128, 128, 128, None),          # LDS-staged row-contiguous epilogue, N % 8 == 0 (gemm.hip ~240)
+    "tiled-n4": ("tiled", 128, 132, 136, None),       # LDS-staged, N % 8 == 4: the 4-column tail form (gemm.hip ~300); 16-byte aligned rows
+    "tiled-bk32": ("tiled", 96, 96, 96, 257 * 128),   # K % 64 != 0 -> BK = 32; 257 row tiles and N % 128 = 96 -> BN = 128: the 64 x 64 fp32
+                                                      # sub-tiles do not fit the BK = 32 staging LDS -> per-lane fallback form (gemm.hip ~385)
+    "tiled-unaligned": ("tiled", 128, 128, 132, None),  # aux (and bf16 output) rows 4 mod 8 elements: not 16-byte aligned -> fallback form
+    "pk": (("pk", 0), 384, 384, 384, None),           # csrc/gemm_pk.hip
+    "ws": ("ws", 384, 384, 384, None),                # csrc/gemm_ws.hip (bf16 output only)
+    "strip": (("strip", 10, 0), 384, 384, 384, None),  # csrc/gemm_strip.hip (derivative, bf16 output only)
+}
+
+
+def _gelu_gemm_case(ops, form, act, out_f32):
+    route, K, N, ld, M = _GELU_FORMS[form]
+    M = M or -(-_N_BF16 // K)
+    w = _selection_weight(N, K).cuda()
+    if act == 1:
+        a = _all_bf16_filling(M, K)
+        x = a.float()[:, torch.arange(N) % K]
+        aux_src = None
+    else:
+        a = torch.ones(M, K, dtype=BF)
+        x = _all_bf16_filling(M, N).float()
+        aux_src = x.to(BF)
+    go = Guarded((M, ld), torch.float32 if out_f32 else BF, (slice(None), slice(0, N)))
+    ga = Guarded((M, ld), BF, (slice(None), slice(0, N)))
+    if aux_src is not None:
+        ga.view.copy_(aux_src.cuda())
+    with _gemm_route(route):
+        ops.gemm_nt(a.cuda(), w, act=act, aux=ga.view, out=go.view, out_f32=out_f32)
+    go.check(f"{form} act={act} output")
+    ga.check(f"{form} act={act} aux")
+    if act == 1:                                                     # the saved pre-activation is the exact input
+        assert torch.equal(ga.view.cpu(), x.to(BF)), f"{form}: saved pre-activation"
+    return go.view, x
+
+
+@pytest.mark.parametrize("form,out_f32", [("tiled", False), ("tiled", True), ("tiled-n4", False), ("tiled-n4", True), ("tiled-bk32", False),
+                                          ("tiled-bk32", True), ("tiled-unaligned", False), ("tiled-unaligned", True), ("pk", False), ("pk", True),
+                                          ("ws", False)])
+def test_gemm_gelu_epilogue_over_every_bf16(ops, form, out_f32):
+    out, x = _gelu_gemm_case(ops, form, 1, out_f32)
+    _check_gelu(out, x, False, f"gelu {form} {'f32' if out_f32 else 'bf16'}")
+
+
+@pytest.mark.parametrize("form,out_f32", [("tiled", False), ("tiled", True), ("tiled-n4", False), ("tiled-n4", True), ("tiled-bk32", False),
+                                          ("tiled-bk32", True), ("tiled-unaligned", False), ("tiled-unaligned", True), ("pk", False), ("pk", True),
+                                          ("ws", False), ("strip", False)])
+def test_gemm_gelu_derivative_epilogue_over_every_bf16(ops, form, out_f32):
+    out, x = _gelu_gemm_case(ops, form, 2, out_f32)
+    _check_gelu(out, x, True, f"gelu' {form} {'f32' if out_f32 else 'bf16'}")
+
+
+@pytest.mark.parametrize("out_f32", [False, True])
+def test_skinny_and_decode_gemm_gelu_over_every_bf16(ops, out_f32):
+    """gemm_skinny (K = 128, 64-row launches) and dec_gemm (K = 768, decode activation layout; 64 + 21 rows)"""
+    K = 128
+    a = _all_bf16_filling(-(-_N_BF16 // K), K)
+    w = _selection_weight(K, K).cuda()
+    for m0 in range(0, a.shape[0], 64):
+        blk = a[m0:m0 + 64]
+        go = Guarded((blk.shape[0], K + 8), torch.float32 if out_f32 else BF, (slice(None), slice(0, K)))
+        ops.gemm_skinny(blk.cuda(), w, act=1, out=go.view, out_f32=out_f32)
+        go.check(f"skinny rows {m0}")
+        _check_gelu(go.view, blk.float(), False, f"gelu skinny rows {m0}.. {'f32' if out_f32 else 'bf16'}")
+    K = 768
+    a = _all_bf16_filling(-(-_N_BF16 // K), K)
+    wp, bc = ops.dec_pack_weight(_selection_weight(K, K).cuda())
+    for m0 in range(0, a.shape[0], 64):
+        blk = a[m0:m0 + 64]
+        M = blk.shape[0]
+        xd, _ = ops.dec_to_dal(blk.cuda())
+        (o,), _ = ops.dec_gemm(xd, M, K, [dict(wp=wp, bc=bc, N=K)], act=1, out_f32=out_f32)
+        _check_gelu(o if out_f32 else ops.dec_from_dal(o, M, K), blk.float(), False, f"gelu dec_gemm rows {m0}.. {'f32' if out_f32 else 'bf16'}")
+
+
+@pytest.mark.parametrize("N", [64, 68])                 # N % 8 == 0: vector epilogue; N = 68: per-element epilogue
+def test_gemm_fp8_gelu_over_every_e4m3(ops, N):
+    K = 64
+    codes = torch.tensor([c for c in range(256) if c not in (0x7F, 0xFF)] + [0, 0], dtype=torch.uint8).view(4, K)   # every finite e4m3
+    a8 = codes.view(ops.FP8).cuda()
+    w8 = _selection_weight(N, K).float().to(ops.FP8).cuda()
+    c, _ = ops.gemm_nt_fp8(a8, w8, 1.0, act=1)
+    x = a8.float().cpu()[:, torch.arange(N) % K]
+    _check_gelu(c, x, False, f"gelu fp8 N={N}")
