@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark of the CXRMate hot path on MI355X (contract: README of the build driver).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3                      # the headline alone: set-up, warm-up, the timed TF steps, one line
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR    # + what the last timed TF step computed, as DIR/*.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full               # + the NT GEMM roofline and every key below the headline
     python bench.py --gpus N ...                                  # no torchrun environment: starts N ranks itself (before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline `value` and nothing else. `--full` adds the TF step's `roofline` (one extra profiled step after the timed ones) and,
+unless a --no-* option drops them, `scst` (also with N ranks), then on one GPU `forward_only`, `tf_single`, `tf_dropin`, `scst_dropin`, `scst_c5`,
+`beam_generation` and `cpu_baseline`; the headline steps, and what --dump-outputs writes, are the same with and without it.
 
 BASELINE.json `metric` = "SCST steps/sec + TF tokens/sec/GPU, 2-image 384x384 studies":
   * headline (`value`): teacher-forcing tokens/s of the MULTI-image model (reference modules/lightning_modules/multi.py:182-210): 32 studies x 2
@@ -19,6 +24,7 @@ BASELINE.json `metric` = "SCST steps/sec + TF tokens/sec/GPU, 2-image 384x384 st
     every step in all variants: their rows are tokenised and embedded inside the timed step.
   * `tf_single`: configs[1] (single-image studies, batch 32), `forward_only`: bf16 MFMA utilisation of the encoder + decoder FORWARD (the
     north_star's >= 40 % target is defined on it), `cpu_baseline`: the oracle/ restatement of the reference path on the host cores.
+  (`scst` and everything in this list: --full only.)
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -698,10 +704,12 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="studies per GPU")
     ap.add_argument("--seq-len", type=int, default=256)
     ap.add_argument("--images", type=int, default=2, help="images per study of the headline teacher-forcing workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scst", action="store_true", help="skip the SCST measurement")
-    ap.add_argument("--no-extras", action="store_true", help="skip tf_single and forward_only")
-    ap.add_argument("--no-dropin", action="store_true", help="skip tf_dropin / scst_dropin (the reference callers' call sequences on the drop-in classes)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the TF step's GEMM roofline, scst, forward_only, tf_single, "
+                    "tf_dropin, scst_dropin, scst_c5, beam_generation and cpu_baseline (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-scst", action="store_true", help="with --full: skip the SCST measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip every one-GPU key but scst and cpu_baseline")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip tf_dropin / scst_dropin (the reference callers' call sequences on the drop-in classes)")
     ap.add_argument("--scst-steps", type=int, default=10)
     ap.add_argument("--graph", action="store_true", help="replay the TF step from hipGraphs (3 segments)")
     ap.add_argument("--eval-mode", action="store_true", help="run the steps under model.eval() (running-statistics BatchNorm, no dropout)")
@@ -751,24 +759,13 @@ def main():
     model = (MultiCXREncoderDecoderModel if N > 1 else SingleCXREncoderDecoderModel)(cfg, device=dev, seed=0)
     if not args.eval_mode:
         model.train()
-    main_res = tf_bench(args, rank, world, dev, model, N, args.steps, profile_gemm=True, dump=bool(args.dump_outputs) and rank == 0)
+    main_res = tf_bench(args, rank, world, dev, model, N, args.steps, profile_gemm=args.full, dump=bool(args.dump_outputs) and rank == 0)
     if "dump" in main_res:
         import numpy as np
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, arr in main_res.pop("dump").items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     ms_per_step, tokens_per_s = main_res["ms_per_step"], main_res["tokens_per_s"]
-    gm = main_res["gemm"]
-    traffic, traffic_src = None, None                        # HBM-side bytes per launch from the committed PMC passes (cannot be collected live)
-    for name in ("r06_pmc_tf_hbm_traffic.json", "r04_pmc_tf_hbm_traffic.json", "r03_pmc_tf_hbm_traffic.json", "r02_pmc_tf_hbm_traffic.json", "r01_pmc_hbm_traffic.json"):
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-            traffic = pmc["gemm_nt"]["hbm_bytes_per_launch"]
-            traffic_src = f"profiles/{name} (FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes" + ("" if not name.startswith("r01") else "; collected on configs[1] in round 1") + ")"
-            break
-        except Exception:
-            pass
-    achieved = gm["nt_flops"] / (gm["nt_ms"] * 1e-3) / 1e12
     mode = ("eval-mode BatchNorm (running statistics), dropout off" if args.eval_mode else
             "model.train(): batch-statistics BatchNorm + running-stat update, dropout 0.1 (hidden + attention probabilities), DropPath")
     out = {
@@ -783,17 +780,30 @@ def main():
                    "rccl_ranks": world, "launch": "hipGraph replay (3 segments, RCCL between)" if args.graph else "eager, weight-gradient kernels on a side stream",
                    "mode": mode, "loss": main_res["loss"], "tokens_per_sec_per_gpu": tokens_per_s / world,
                    "model_tflops_per_gpu": main_res["step_gflop_per_gpu"] * 1e-3 / (ms_per_step * 1e-3)},
-        "roofline": {"bound": "mfma", "kernel": "NT GEMM family (gemm_nt_kernel tile variants, gemm_nt_group_kernel, the row-strip kernel gemm_strip384_kernel for the 384- / "
-                               "192-wide outputs of CvT stages 3 / 2, and in the forward pass the persistent gemm_nt_pk_kernel / gemm_ws384_kernel; "
-                               "v_mfma_f32_16x16x32_bf16), timed while the weight-gradient stream runs beside it, as in the timed region", "achieved": achieved,
-                     "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TF, "traffic": traffic,
-                     "traffic_unit": "bytes per launch", "traffic_source": traffic_src, "algorithmic_bytes_per_launch": gm["nt_bytes"] / max(1, gm["nt_n"]),
-                     "launches_per_step": gm["nt_n"], "avg_launch_us": gm["nt_ms"] * 1e3 / max(1, gm["nt_n"]),
-                     "avg_launch_gflop": gm["nt_flops"] / max(1, gm["nt_n"]) * 1e-9, "gemm_share_of_step": gm["nt_ms"] / ms_per_step,
-                     "weight_grad_kernel": {"kernel": "gemm_tn_kernel (128x128 tiles) / gemm_tn2_kernel (256x256 blocks, long token runs) / gemm_tn5_kernel (384x192 blocks, CvT stage 3)", "launches_per_step": gm["tn_n"],
-                                            "achieved": gm["tn_flops"] / (gm["tn_ms"] * 1e-3) / 1e12 if gm["tn_ms"] else None,
-                                            "avg_launch_us": gm["tn_ms"] * 1e3 / max(1, gm["tn_n"])}},
     }
+    if not args.full:                                        # a plain run: the headline alone
+        return report(out, rank, world)
+    gm = main_res["gemm"]
+    traffic, traffic_src = None, None                        # HBM-side bytes per launch from the committed PMC passes (cannot be collected live)
+    for name in ("r06_pmc_tf_hbm_traffic.json", "r04_pmc_tf_hbm_traffic.json", "r03_pmc_tf_hbm_traffic.json", "r02_pmc_tf_hbm_traffic.json", "r01_pmc_hbm_traffic.json"):
+        try:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+            traffic = pmc["gemm_nt"]["hbm_bytes_per_launch"]
+            traffic_src = f"profiles/{name} (FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes" + ("" if not name.startswith("r01") else "; collected on configs[1] in round 1") + ")"
+            break
+        except Exception:
+            pass
+    achieved = gm["nt_flops"] / (gm["nt_ms"] * 1e-3) / 1e12
+    out["roofline"] = {"bound": "mfma", "kernel": "NT GEMM family (gemm_nt_kernel tile variants, gemm_nt_group_kernel, the row-strip kernel gemm_strip384_kernel for the 384- / "
+                                 "192-wide outputs of CvT stages 3 / 2, and in the forward pass the persistent gemm_nt_pk_kernel / gemm_ws384_kernel; "
+                                 "v_mfma_f32_16x16x32_bf16), timed while the weight-gradient stream runs beside it, as in the timed region", "achieved": achieved,
+                       "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TF, "traffic": traffic,
+                       "traffic_unit": "bytes per launch", "traffic_source": traffic_src, "algorithmic_bytes_per_launch": gm["nt_bytes"] / max(1, gm["nt_n"]),
+                       "launches_per_step": gm["nt_n"], "avg_launch_us": gm["nt_ms"] * 1e3 / max(1, gm["nt_n"]),
+                       "avg_launch_gflop": gm["nt_flops"] / max(1, gm["nt_n"]) * 1e-9, "gemm_share_of_step": gm["nt_ms"] / ms_per_step,
+                       "weight_grad_kernel": {"kernel": "gemm_tn_kernel (128x128 tiles) / gemm_tn2_kernel (256x256 blocks, long token runs) / gemm_tn5_kernel (384x192 blocks, CvT stage 3)", "launches_per_step": gm["tn_n"],
+                                              "achieved": gm["tn_flops"] / (gm["tn_ms"] * 1e-3) / 1e12 if gm["tn_ms"] else None,
+                                              "avg_launch_us": gm["tn_ms"] * 1e3 / max(1, gm["tn_n"])}}
     # the second workload of BASELINE.json with a number of its own (configs[3]) is measured right behind the headline, in front of the auxiliary keys: on
     # some boxes of the pool its MFMA-heavy phases run up to 8 ms per step slower after the long MFMA-heavy prelude the auxiliary TF keys make
     # (profiles/r04_ab_wgrad_stream.txt, calls 33 / 34); the headline key is measured first either way
@@ -857,6 +867,11 @@ def main():
             out["cpu_baseline"] = cpu_baseline(T, V, N)
         except Exception as e:                              # the baseline must never take the GPU number down with it
             out["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": torch.get_num_threads(), "kind": "port", "sample": f"failed: {e}"}
+    report(out, rank, world)
+
+
+def report(out, rank, world):
+    """Rank 0 prints the ONE JSON line; the process group is torn down."""
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

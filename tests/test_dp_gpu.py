@@ -436,9 +436,9 @@ def test_dp_rehearsal_ranks_share_one_device():
 
 
 def test_bench_multi_gpu_rehearsal_and_refusal():
-    """`bench.py --gpus N` end to end with N = REHEARSAL_RANKS ranks on the one GPU (CXR_BENCH_REHEARSAL=1: tiny configuration; gloo; every rank on
-    device 0): spawn_ranks finds a port, hands each rank its slice of the host cores, the ranks rendezvous, run the TF and SCST keys with their
-    all-reduces / gather, and rank 0 prints ONE JSON line for n_gpus = N that says it is a rehearsal. A process group whose size is not N is
+    """`bench.py --gpus N --full` end to end with N = REHEARSAL_RANKS ranks on the one GPU (CXR_BENCH_REHEARSAL=1: tiny configuration; gloo; every
+    rank on device 0): spawn_ranks finds a port, hands each rank its slice of the host cores, the ranks rendezvous, run the TF and SCST keys with
+    their all-reduces / gather, and rank 0 prints ONE JSON line for n_gpus = N that says it is a rehearsal. A process group whose size is not N is
     refused (`--gpus 8` in a one-rank environment)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -451,7 +451,7 @@ def test_bench_multi_gpu_rehearsal_and_refusal():
         env.pop(k, None)
     n = REHEARSAL_RANKS
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "0", "--batch", "2", "--seq-len", "16",
-                        "--scst-steps", "1", "--new-tokens", "9", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                        "--scst-steps", "1", "--new-tokens", "9", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                               # ONE line, from rank 0
@@ -505,3 +505,30 @@ def test_bench_dump_outputs_are_reproducible(tmp_path):
     w0, w1 = (d["tf_master_weights_sample.npy"] for d in dumps)
     lr, updates = 5e-5, 2 + 1 + 3                                        # tf_bench's AdamW; CXR_BENCH_PREWARM + --warmup + --steps
     assert np.abs(w0 - w1).max() <= 2 * lr * updates, float(np.abs(w0 - w1).max())
+
+
+def test_bench_plain_run_measures_the_headline_alone():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (tiny rehearsal configuration, one rank, no --no-* option) measures the headline and
+    nothing else: ONE JSON line with the headline keys and the TF step's config, and none of the keys `--full` adds (the GEMM roofline and its
+    extra profiled step, the SCST keys, the auxiliary workloads, the CPU baseline)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CXR_BENCH_REHEARSAL="1", CXR_BENCH_PREWARM="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--seq-len", "16"],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "tf_tokens_per_sec" and out["unit"] == "tokens/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["ms_per_step"] > 0 and np.isclose(out["value"], 2 * 16 * 1e3 / out["ms_per_step"], rtol=1e-9)       # batch x seq-len tokens per step
+    assert np.isfinite(out["config"]["loss"])
+    moved = {"roofline", "scst", "forward_only", "tf_single", "tf_dropin", "scst_dropin", "scst_c5", "beam_generation", "cpu_baseline"}
+    assert not moved & set(out), sorted(moved & set(out))
