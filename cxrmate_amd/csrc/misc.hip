@@ -117,6 +117,91 @@ extern "C" int cxr_bert_embed_bwd(const void* dsum, const long* ids, const long*
     return CXR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- RoBERTa embeddings (BERTScore trunk)
+// out[b,t] = LayerNorm(word[id] + type[0] + pos[p]) with RoBERTa's position rule (TF5 modeling_roberta.py create_position_ids_from_input_ids):
+// p = padding_idx + #{s <= t : ids[b,s] != padding_idx} for a non-pad token, p = padding_idx for a pad. One wave per row; the wave counts the
+// non-pad ids of its row's prefix itself (<= 512 ids, 8 per lane), so no cumsum pass precedes it. An id outside the word table makes the row NaN
+// instead of reading past the table. C = 768 or 1024, forward only (no dropout, no saved sum).
+template <int C>
+__global__ __launch_bounds__(256) void roberta_embed_fwd_kernel(const long* __restrict__ ids, long B, int T, const bf16_t* __restrict__ word,
+                                                                long vocab, const bf16_t* __restrict__ type, const bf16_t* __restrict__ posw,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                                long padding_idx, bf16_t* __restrict__ out, long* __restrict__ pos_out) {
+    constexpr int CH = C / 8, NCH = (CH + 63) / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long R = B * T;
+    for (long row = (long)blockIdx.x * 4 + wave; row < R; row += (long)gridDim.x * 4) {
+        const long b = row / T;
+        const int t = (int)(row % T);
+        const long* seq = ids + b * T;
+        int cnt = 0;
+        for (int s = lane; s <= t; s += 64) cnt += seq[s] != padding_idx;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        const long id = seq[t];
+        const long ps = id != padding_idx ? padding_idx + cnt : padding_idx;
+        if (pos_out && lane == 0) pos_out[row] = ps;
+        const bool bad = id < 0 || id >= vocab;
+        const long idc = bad ? 0 : id;
+        float v[NCH][8];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int ch = lane + i * 64;
+            if (ch < CH) {
+                float a[8], bb[8], c[8];
+                unpack8(*reinterpret_cast<const uint4*>(word + idc * C + ch * 8), a);
+                unpack8(*reinterpret_cast<const uint4*>(type + ch * 8), bb);
+                unpack8(*reinterpret_cast<const uint4*>(posw + ps * C + ch * 8), c);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { v[i][j] = (a[j] + bb[j]) + c[j]; s += v[i][j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+            }
+        }
+        const float mean = group_sum<64>(s) * (1.0f / C);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+            if (lane + i * 64 < CH) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q += d * d; }
+            }
+        const float rstd = bad ? __builtin_nanf("") : rsqrtf(group_sum<64>(q) * (1.0f / C) + eps);
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int ch = lane + i * 64;
+            if (ch < CH) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * gamma[ch * 8 + j] + beta[ch * 8 + j];
+                *reinterpret_cast<uint4*>(out + row * C + ch * 8) = pack8(o);
+            }
+        }
+    }
+}
+
+extern "C" int cxr_roberta_embed_fwd(const long* ids, long B, int T, const void* word, long vocab, const void* type, const void* posw, long n_pos,
+                                     const float* gamma, const float* beta, float eps, long padding_idx, void* out, long* pos_out, int C,
+                                     hipStream_t stream) {
+    // the largest position is padding_idx + T: it must be a row of the position table
+    if (B <= 0 || T <= 0 || vocab <= 0 || padding_idx < 0 || padding_idx + T >= n_pos || !ids || !word || !type || !posw || !gamma || !beta || !out)
+        return CXR_ERR_ARG;
+    const long R = B * T;
+    const int grid = (int)(cdiv(R, 4) < 4096 ? cdiv(R, 4) : 4096);
+    if (C == 768)
+        CXR_LAUNCH(roberta_embed_fwd_kernel<768>, dim3(grid), dim3(256), 0, stream, ids, B, T, (const bf16_t*)word, vocab, (const bf16_t*)type,
+                   (const bf16_t*)posw, gamma, beta, eps, padding_idx, (bf16_t*)out, pos_out);
+    else if (C == 1024)
+        CXR_LAUNCH(roberta_embed_fwd_kernel<1024>, dim3(grid), dim3(256), 0, stream, ids, B, T, (const bf16_t*)word, vocab, (const bf16_t*)type,
+                   (const bf16_t*)posw, gamma, beta, eps, padding_idx, (bf16_t*)out, pos_out);
+    else
+        return CXR_ERR_ARG;
+    CXR_LAUNCH_CHECK();
+    return CXR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- token-type / position ids (K15) -- bit-exact
 // reference modelling_longitudinal.py:297-338: for each special id (in order) the section after its FIRST occurrence (excluded when that
 // occurrence is column 0 or the last column) gets sections[i+1]; later special ids overwrite earlier ones.

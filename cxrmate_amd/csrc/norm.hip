@@ -309,7 +309,10 @@ extern "C" int cxr_layernorm_fwd_bf16(const void* x, long ldx, const float* gamm
                                       float* stats, long rows, int C, float eps, hipStream_t stream) {
     if (rows <= 0 || (ldx % 8) || (ldy % 8)) return CXR_ERR_ARG;
     const int grid = ln_grid(rows, C, (C == 64 || C == 128) ? 4 : 2, true);
-    LN_DISPATCH(C, layernorm_fwd_kernel, 4, 4, 2, 2, 2, (const bf16_t*)x, ldx, gamma, beta, (bf16_t*)y, ldy, stats, rows, eps);
+    if (C == 1024)          // RoBERTa-large width (BERTScore trunk), forward only: 128 chunks = 2 per lane of a full wave, one row per wave
+        CXR_LAUNCH((layernorm_fwd_kernel<1024, 2>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, ldx, gamma, beta, (bf16_t*)y, ldy, stats, rows, eps);
+    else
+        LN_DISPATCH(C, layernorm_fwd_kernel, 4, 4, 2, 2, 2, (const bf16_t*)x, ldx, gamma, beta, (bf16_t*)y, ldy, stats, rows, eps);
     CXR_LAUNCH_CHECK();
     return CXR_OK;
 }

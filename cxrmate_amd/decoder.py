@@ -89,8 +89,11 @@ class KVCache:
 
 
 class BertEngine:
-    def __init__(self, store, cfg: BertConfig, prefix: str = "decoder."):
+    def __init__(self, store, cfg: BertConfig, prefix: str = "decoder.", roberta_embeddings: bool = False):
+        """roberta_embeddings: RobertaEmbeddings instead of BertEmbeddings (positions from the ids by RoBERTa's rule, padding_idx =
+        cfg.pad_token_id, token type 0; forward-only eval passes) -- the BERTScore trunk (bertscore.py)."""
         self.s, self.cfg = store, cfg
+        self.roberta_embeddings = bool(roberta_embeddings)
         self.p = prefix + ("base_model.model." if cfg.lora_r else "")
         self._prep_version = -1
         self._prep = {}
@@ -261,10 +264,18 @@ class BertEngine:
         need_lse = save or want_attn
         pl, ls = float(cfg.lora_dropout), (cfg.lora_alpha / cfg.lora_r if cfg.lora_r else 0.0)
         e = p + "bert.embeddings."
-        h, esum, estats = ops.bert_embed(ids, token_type_ids, position_ids, st.w16(e + "word_embeddings.weight") if word is None else word,
-                                         st.w16(e + "token_type_embeddings.weight"), st.w16(e + "position_embeddings.weight"),
-                                         st.f32(e + "LayerNorm.weight"), st.f32(e + "LayerNorm.bias"), cfg.layer_norm_eps, T, need_sum=save,
-                                         drop=(ph, seed, SITE_EMBED) if ph else None)
+        if self.roberta_embeddings:
+            if save or ph or word is not None or token_type_ids is not None or position_ids is not None:
+                raise ValueError("the RoBERTa embeddings run forward-only in eval mode, from input ids alone")
+            h = ops.roberta_embed(ids.contiguous(), st.w16(e + "word_embeddings.weight"), st.w16(e + "token_type_embeddings.weight"),
+                                  st.w16(e + "position_embeddings.weight"), st.f32(e + "LayerNorm.weight"), st.f32(e + "LayerNorm.bias"),
+                                  cfg.layer_norm_eps, cfg.pad_token_id)
+            esum = estats = None
+        else:
+            h, esum, estats = ops.bert_embed(ids, token_type_ids, position_ids, st.w16(e + "word_embeddings.weight") if word is None else word,
+                                             st.w16(e + "token_type_embeddings.weight"), st.w16(e + "position_embeddings.weight"),
+                                             st.f32(e + "LayerNorm.weight"), st.f32(e + "LayerNorm.bias"), cfg.layer_norm_eps, T, need_sum=save,
+                                             drop=(ph, seed, SITE_EMBED) if ph else None)
         if want_hidden:
             extra["hidden"].append(h)
         saved = dict(B=B, T=T, ids=ids, tt=token_type_ids, pos=position_ids, esum=esum, estats=estats, attn_mask=attn_mask, enc=enc,

@@ -998,6 +998,21 @@ def bert_embed_bwd(dsum, ids, tt, pid, dword, dtype_, dpos, T, pos_offset, paddi
                                  int(padding_idx), dsum.shape[1], _s()), dsum, ids, tt, pid, dword, dtype_, dpos)
 
 
+def roberta_embed(ids, word, typ, posw, gamma, beta, eps, padding_idx, pos_out=False):
+    """RobertaEmbeddings forward (eval): ids int64 [B, T] -> LayerNorm(word[id] + type[0] + pos[p]) bf16 [B*T, C], positions from RoBERTa's
+    rule computed in the kernel (pos_out=True: also the positions, int64 [B, T])."""
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.is_contiguous()
+    for t in (word, typ, posw):
+        assert t.dtype == BF16 and t.is_contiguous()
+    B, T = ids.shape
+    C = word.shape[1]
+    out = torch.empty((B * T, C), device=ids.device, dtype=BF16)
+    pos = torch.empty((B, T), device=ids.device, dtype=torch.int64) if pos_out else None
+    LIB.call("cxr_roberta_embed_fwd", _p(ids), B, T, _p(word), word.shape[0], _p(typ), _p(posw), posw.shape[0], _p(gamma), _p(beta), float(eps),
+             int(padding_idx), _p(out), _p(pos), C, _s())
+    return (out, pos) if pos_out else out
+
+
 _SPECIAL_CACHE = {}
 
 
@@ -1614,3 +1629,18 @@ def lora_outer_into(a, t, G, g_ks, g_rs, scale=1.0, drop=None, rows_per_b=1, tpo
     p, site = drop if drop is not None else (0.0, 0)
     LIB.call("cxr_lora_outer_bf16", _p(a), a.stride(0), M, K, _p(t), _p(G), int(g_ks), int(g_rs), float(scale), float(p), _p(seed), int(site),
              int(rows_per_b), int(tpos0), _s())
+
+
+def bertscore_match(hidden, sent, pairs, weights, floors):
+    """BERTScore greedy matching of `pairs` over the rows of `hidden` (see cxr_bertscore_match). hidden bf16 [rows, D]; sent int32 [n, 2]
+    (first row, length); pairs int32 [m, 2] (hyp sentence, ref sentence); weights fp32 [rows]; floors uint8 [m, 2] -> raw P, R, F fp32 [m]."""
+    assert hidden.dtype == BF16 and hidden.dim() == 2 and hidden.is_contiguous()
+    assert sent.dtype == torch.int32 and sent.dim() == 2 and sent.shape[1] == 2 and sent.is_contiguous()
+    assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous()
+    assert weights.dtype == torch.float32 and weights.shape == (hidden.shape[0],) and weights.is_contiguous()
+    assert floors.dtype == torch.uint8 and floors.shape == pairs.shape and floors.is_contiguous()
+    m = pairs.shape[0]
+    out = torch.empty((3, m), dtype=torch.float32, device=hidden.device)
+    LIB.call("cxr_bertscore_match", _p(hidden), hidden.shape[0], hidden.shape[1], _p(sent), sent.shape[0], _p(pairs), _p(weights), _p(floors), m,
+             _p(out[0]), _p(out[1]), _p(out[2]), _s())
+    return out[0], out[1], out[2]

@@ -465,6 +465,19 @@ int cxr_pixels_u8_to_f32(const void* src, const long* first_image, float* dst, i
  * the stacked head logits (lowest index wins ties, like torch.argmax); offsets int32 [nseg+1], out int64 [R][nseg]. */
 int cxr_segment_argmax_f32(const float* x, long ld, const int* offsets, int nseg, long* out, long R, hipStream_t stream);
 
+/* ---- RoBERTa embeddings (TF5:roberta RobertaEmbeddings, forward only): out[b,t] = LayerNorm(word[id] + type[0] + pos[p]) with RoBERTa's
+ * position rule computed on the device: p = padding_idx + #{s <= t : ids[b,s] != padding_idx} for a non-pad token, padding_idx for a pad
+ * (pos_out int64 [B*T], optional, receives p). ids int64 [B][T]; C = 768 or 1024; padding_idx + T < n_pos; an id outside [0, vocab) gives a NaN row. */
+int cxr_roberta_embed_fwd(const long* ids, long B, int T, const void* word, long vocab, const void* type, const void* posw, long n_pos,
+                          const float* gamma, const float* beta, float eps, long padding_idx, void* out, long* pos_out, int C, hipStream_t stream);
+
+/* ---- BERTScore greedy matching (bert_score greedy_cos_idf, idf=False): hidden bf16 [n_rows][D] (D = 768 or 1024) holds the last hidden states
+ * of every distinct sentence; sent int32 [n_sent][2] = (first row, length 1..512); pairs int32 [n_pairs][2] = (hyp sentence, ref sentence);
+ * weights fp32 [n_rows] per token; floors uint8 [n_pairs][2] = (floor the precision row maxima at 0, floor the recall column maxima at 0) -- the
+ * zero entries the reference's chunk padding puts into the max. -> raw P, R, F fp32 [n_pairs]; a table entry outside the buffer gives NaN. */
+int cxr_bertscore_match(const void* hidden, long n_rows, int D, const int* sent, int n_sent, const int* pairs, const float* weights,
+                        const unsigned char* floors, int n_pairs, float* P, float* R, float* F, hipStream_t stream);
+
 /* ---- cached-decode step inputs in one launch (REF:modelling_longitudinal.py:251-295 prepare_inputs_for_generation and its single / multi
  * copies): from ids[r, strip:cur] -> new_id = last token, tt = token_ids_to_token_type_ids_past (:340-364; rows < half_rows use special0, the
  * rest special1), mask = ids != mask_token_id and pos = relu(cumsum(mask)-1)[-1] (:274-277; mask == NULL skips both); tt / pos are also written
