@@ -123,3 +123,39 @@ class CheXbert:
             reports[i] = reports[i].strip()
         tok = self.tokenizer(reports, padding="longest", return_tensors="pt", truncation=True, max_length=self.config.max_position_embeddings)
         return self.label_ids(tok["input_ids"], tok["attention_mask"], tok.get("token_type_ids"))[0]
+
+    @torch.no_grad()
+    def label_all(self, texts, mbatch_size):
+        """Labels of a whole epoch, int64 [len(texts), 14] on the device: the clean-up lines of `forward`, ONE tokenizer call, longest-first
+        mini-batches of `mbatch_size` rows (each pads to its own longest row, not to the epoch's), the original order restored on the device.
+        The caller passes each distinct text once (metrics.CheXbertClassificationMetrics does)."""
+        if self.tokenizer is None:
+            raise RuntimeError("CheXbert needs the bert-base-uncased tokenizer (not available offline): pass tokenizer=...")
+        out = torch.empty((len(texts), len(HEAD_CLASSES)), dtype=torch.int64, device=self.device)
+        if not len(texts):
+            return out
+        clean = []
+        for t in texts:                                                 # reference tools/chexbert.py:53-58 (the caller's list is left alone)
+            t = t.strip()
+            t = t.replace("\n", " ")
+            t = t.replace("\\s+", " ")
+            t = t.replace("\\s+(?=[\\.,])", "")
+            clean.append(t.strip())
+        tok = self.tokenizer(clean, add_special_tokens=True, padding=False, truncation=True, max_length=self.config.max_position_embeddings)
+        enc, types = tok["input_ids"], tok.get("token_type_ids")
+        order = sorted(range(len(enc)), key=lambda i: -len(enc[i]))
+        pad_id = getattr(self.tokenizer, "pad_token_id", 0) or 0
+        mb = max(int(mbatch_size), 1)
+        for lo in range(0, len(order), mb):
+            idx = order[lo:lo + mb]
+            width = len(enc[idx[0]])
+            ids = torch.full((len(idx), width), pad_id, dtype=torch.int64)
+            mask = torch.zeros((len(idx), width), dtype=torch.int64)
+            tt = None if types is None else torch.zeros((len(idx), width), dtype=torch.int64)
+            for r, i in enumerate(idx):
+                ids[r, :len(enc[i])] = torch.tensor(enc[i], dtype=torch.int64)
+                mask[r, :len(enc[i])] = 1
+                if tt is not None:
+                    tt[r, :len(enc[i])] = torch.tensor(types[i], dtype=torch.int64)
+            out[torch.tensor(idx, device=self.device)] = self.label_ids(ids, mask, tt)[0]
+        return out

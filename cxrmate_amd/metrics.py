@@ -1,4 +1,6 @@
-"""CXR-BERT similarity metric on MI355X -- the evaluation-time consumer of the reward kernels (reference tools/metrics/cxr_bert.py:10-184).
+"""Test-stage metrics on MI355X: `CXRBERT` (below) and `CheXbertClassificationMetrics` (its own docstring).
+
+CXR-BERT similarity metric -- the evaluation-time consumer of the reward kernels (reference tools/metrics/cxr_bert.py:10-184).
 
 Behaviour kept from the reference's torchmetrics `CXRBERT(split, ckpt_dir, mbatch_size, exp_dir, accumulate_over_dicoms)`:
   * `update(predictions, labels, study_ids, dicom_ids=None)` checks its arguments the way the reference does and collects the reports;
@@ -126,3 +128,127 @@ class CXRBERT:
             _, inv = np.unique(table["study_id"].astype(str), return_inverse=True)
             scores = np.bincount(inv, weights=scores) / np.bincount(inv)
         return float(scores.mean())
+
+
+# ================================================================================================ CheXbert classification metrics
+PATHOLOGIES = [
+    "enlarged_cardiomediastinum", "cardiomegaly", "lung_opacity", "lung_lesion", "edema", "consolidation", "pneumonia", "atelectasis",
+    "pneumothorax", "pleural_effusion", "pleural_other", "fracture", "support_devices", "no_finding",
+]
+_ERRORS = ("tp", "tn", "fp", "fn")
+_RATIOS = ("accuracy", "precision", "recall", "f1")
+
+
+def _plain(v):
+    return v.item() if hasattr(v, "item") else v
+
+
+def merge_label_parts(parts, accumulate_over_dicoms):
+    """The host step between labelling and scoring, as a pure function of the per-rank parts (rank order). A part is a dict: `pred` int64 [n, 14]
+    (one row per record), `ref` int64 [u, 14] (one row per distinct label text of that rank), `ref_row` [n] (each record's row in `ref`),
+    `study_id` [n] and, when accumulating, `dicom_id` [n].
+    -> dict: `pred` / `ref` the concatenated tables; `pred_row`, `ref_row` int32 [M], `study_id`, `dicom_id` (lists): the kept records -- the
+    first per DICOM, or per study when not accumulating -- in order of appearance; `order` int64 [M]: those records grouped by study, the
+    studies sorted by id when accumulating (pandas groupby) and in order of first appearance otherwise; `studies`: the S ids in that order;
+    `study_off` int32 [S + 1]: CSR offsets into `order`."""
+    pred = np.concatenate([np.asarray(p["pred"], dtype=np.int64).reshape(-1, len(PATHOLOGIES)) for p in parts])
+    ref = np.concatenate([np.asarray(p["ref"], dtype=np.int64).reshape(-1, len(PATHOLOGIES)) for p in parts])
+    ref_base = np.cumsum([0] + [len(p["ref"]) for p in parts])
+    ref_row = np.concatenate([np.asarray(p["ref_row"], dtype=np.int64) + b for p, b in zip(parts, ref_base)])
+    study = [_plain(v) for p in parts for v in p["study_id"]]
+    dicom = [_plain(v) for p in parts for v in p["dicom_id"]] if accumulate_over_dicoms else None
+    seen, keep = set(), []
+    for i, k in enumerate(dicom if accumulate_over_dicoms else study):     # one row per DICOM / study: DDP pads the last batch with repeats
+        if k not in seen:
+            seen.add(k)
+            keep.append(i)
+    kept_study = [study[i] for i in keep]
+    first = {}
+    for s in kept_study:
+        first.setdefault(s, len(first))
+    studies = sorted(first) if accumulate_over_dicoms else list(first)
+    rank = {s: r for r, s in enumerate(studies)}
+    group = np.array([rank[s] for s in kept_study], dtype=np.int64)
+    order = np.argsort(group, kind="stable")
+    study_off = np.concatenate([[0], np.cumsum(np.bincount(group, minlength=len(studies)))]).astype(np.int32)
+    return {"pred": pred, "ref": ref, "pred_row": np.asarray(keep, dtype=np.int32), "ref_row": ref_row[keep].astype(np.int32),
+            "study_id": kept_study, "dicom_id": [dicom[i] for i in keep] if accumulate_over_dicoms else None, "order": order,
+            "studies": studies, "study_off": study_off}
+
+
+class CheXbertClassificationMetrics:
+    """CheXbert classification metrics (reference tools/metrics/chexbert.py:34-336, the source of `val_report_chexbert_f1_macro`).
+
+    Behaviour kept from the reference's torchmetrics `CheXbertClassificationMetrics(split, ckpt_dir, bert_path, checkpoint_path, mbatch_size, exp_dir,
+    accumulate_over_dicoms)`: the update / compute / reset surface, the labeller built in `compute`, rows of all ranks merged in rank order, one row per
+    DICOM / study, each error type averaged over the DICOMs of a study, the four CSVs under `<exp_dir>/chexbert_outputs` and the returned dict (12
+    averaged scores, 56 per-pathology scores, `num_study_ids`, `num_dicom_ids`). How it is computed is this build's own: columnar state, every
+    prediction and every DISTINCT label text labelled once over the whole epoch (`CheXbert.label_all`), only the two small class-index tables cross to
+    the host, and everything pandas derives from them is one call of `cxr_chexbert_scores` (csrc/chexbert_metric.hip)."""
+
+    def __init__(self, split, ckpt_dir, bert_path, checkpoint_path, mbatch_size, exp_dir, accumulate_over_dicoms, chexbert=None, device=None):
+        self.split, self.ckpt_dir, self.bert_path, self.checkpoint_path = split, ckpt_dir, bert_path, checkpoint_path
+        self.mbatch_size, self.exp_dir = int(mbatch_size), exp_dir
+        self.accumulate_over_dicoms = bool(accumulate_over_dicoms)
+        self.chexbert = chexbert
+        self.device = torch.device(device) if device is not None else (chexbert.device if chexbert is not None else None)
+        self.save_dir = os.path.join(self.exp_dir, "chexbert_outputs")
+        os.makedirs(self.save_dir, exist_ok=True)
+        self.reset()
+
+    # ------------------------------------------------------------------------------------------ state (CXRBERT's: same columns, checks and messages)
+    reset = CXRBERT.reset
+    reports = CXRBERT.reports
+    mini_batch = staticmethod(CXRBERT.mini_batch)
+    update = CXRBERT.update
+
+    # ------------------------------------------------------------------------------------------ scoring
+    def _write(self, kind, epoch, header, rows):
+        path = os.path.join(self.save_dir, f'{self.split}_epoch-{epoch}_{kind}_{time.strftime("%d-%m-%Y_%H-%M-%S")}.csv')
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(header)
+            w.writerows(rows)
+
+    def compute(self, epoch):
+        from . import ops
+        chexbert = self.chexbert
+        if chexbert is None:                                    # as the reference: built here, from the checkpoint (tools/metrics/chexbert.py:108-113)
+            from .chexbert import CheXbert
+            chexbert = CheXbert(self.ckpt_dir, self.bert_path, self.checkpoint_path, self.device if self.device is not None else "cuda")
+        for group in self._label:                               # following COCO the label of a report is a one-element list (:124-127)
+            assert len(group) == 1
+        uniq = {}
+        label_row = [uniq.setdefault(group[0], len(uniq)) for group in self._label]      # every distinct label text is labelled once
+        pred = chexbert.label_all(list(self._pred), self.mbatch_size)
+        ref = chexbert.label_all(list(uniq), self.mbatch_size)
+        part = {"pred": pred.cpu().numpy(), "ref": ref.cpu().numpy(), "ref_row": np.asarray(label_row, dtype=np.int64),
+                "study_id": list(self._study)}
+        if self.accumulate_over_dicoms:
+            part["dicom_id"] = list(self._dicom)
+        parts = [part]
+        if _is_dist():                                          # parts of all ranks, rank order (reference: all_gather_object of the row dicts)
+            parts = [None] * torch.distributed.get_world_size()
+            torch.distributed.all_gather_object(parts, part)
+        m = merge_label_parts(parts, self.accumulate_over_dicoms)
+        dev = pred.device
+        order = m["order"]
+        example, cls, avg = ops.chexbert_scores(torch.from_numpy(m["pred"]).to(dev), torch.from_numpy(m["ref"]).to(dev),
+                                                torch.from_numpy(m["pred_row"][order]).to(dev), torch.from_numpy(m["ref_row"][order]).to(dev),
+                                                torch.from_numpy(m["study_off"]).to(dev))
+        example, cls, avg = example.cpu().numpy(), cls.cpu().numpy(), avg.cpu().numpy()
+        class_keys = [f"{r}_{p}" for r in _RATIOS for p in PATHOLOGIES]                      # the reference's melted column names
+        class_vals = [float(cls[j, 4 + k]) for k in range(len(_RATIOS)) for j in range(len(PATHOLOGIES))]
+        if not _is_dist() or torch.distributed.get_rank() == 0:
+            ids = ["dicom_id", "study_id"] if self.accumulate_over_dicoms else ["study_id"]
+            id_cols = ([m["dicom_id"]] if self.accumulate_over_dicoms else []) + [m["study_id"]]
+            for kind, table, rows in (("y_hat", m["pred"], m["pred_row"]), ("y", m["ref"], m["ref_row"])):
+                self._write(kind, epoch, ids + PATHOLOGIES, [list(i) + table[r].tolist() for *i, r in zip(*id_cols, rows)])
+            self._write("class_scores", epoch, class_keys, [class_vals])
+            self._write("example_scores", epoch, ["study_id", *_ERRORS, *_RATIOS], [[s] + example[i].tolist() for i, s in enumerate(m["studies"])])
+        score = {f"{r}_{a}": float(avg[4 * j + k]) for j, a in enumerate(("example", "macro", "micro")) for k, r in enumerate(_RATIOS)}
+        score.update(zip(class_keys, class_vals))
+        score["num_study_ids"] = float(len(m["studies"]))
+        if self.accumulate_over_dicoms:
+            score["num_dicom_ids"] = float(len(set(m["dicom_id"])))
+        return score

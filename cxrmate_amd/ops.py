@@ -1644,3 +1644,22 @@ def bertscore_match(hidden, sent, pairs, weights, floors):
     LIB.call("cxr_bertscore_match", _p(hidden), hidden.shape[0], hidden.shape[1], _p(sent), sent.shape[0], _p(pairs), _p(weights), _p(floors), m,
              _p(out[0]), _p(out[1]), _p(out[2]), _s())
     return out[0], out[1], out[2]
+
+
+def chexbert_scores(pred, ref, pred_row, ref_row, study_off):
+    """CheXbert classification scores from the labeller's tables (see cxr_chexbert_scores). pred int64 [n_pred, 14]; ref int64 [n_ref, 14];
+    pred_row / ref_row int32 [M] (table rows of the kept records, grouped by study); study_off int32 [S + 1] -> float64 example [S, 8],
+    cls [14, 8] (tp, tn, fp, fn, accuracy, precision, recall, f1) and avg [12] ({accuracy, precision, recall, f1} x {example, macro, micro})."""
+    for t in (pred, ref):
+        assert t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 14 and t.is_contiguous()
+    for t in (pred_row, ref_row, study_off):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    assert pred_row.shape == ref_row.shape
+    M, S = pred_row.shape[0], study_off.shape[0] - 1
+    example = torch.empty((max(S, 0), 8), dtype=torch.float64, device=pred.device)
+    cls = torch.empty((14, 8), dtype=torch.float64, device=pred.device)
+    avg = torch.empty((12,), dtype=torch.float64, device=pred.device)
+    ws = torch.empty((56 * max(S, 0) + 64,), dtype=torch.float64, device=pred.device)
+    LIB.call("cxr_chexbert_scores", _p(pred), pred.shape[0], _p(ref), ref.shape[0], _p(pred_row), _p(ref_row), M, _p(study_off), S, _p(example),
+             _p(cls), _p(avg), _p(ws), ws.numel() * 8, _s())
+    return example, cls, avg

@@ -478,6 +478,17 @@ int cxr_roberta_embed_fwd(const long* ids, long B, int T, const void* word, long
 int cxr_bertscore_match(const void* hidden, long n_rows, int D, const int* sent, int n_sent, const int* pairs, const float* weights,
                         const unsigned char* floors, int n_pairs, float* P, float* R, float* F, hipStream_t stream);
 
+/* ---- CheXbert classification scores (REF:tools/metrics/chexbert.py:191-336) from the labeller's tables. pred int64 [n_pred][14] / ref int64
+ * [n_ref][14]: class indices as cxr_segment_argmax_f32 writes them (positive = 1). pred_row / ref_row int32 [M]: the table rows of every kept
+ * record, records grouped by study; study_off int32 [S+1]: CSR offsets. All outputs float64: example [S][8] and cls [14][8] = (tp, tn, fp, fn,
+ * accuracy, precision, recall, f1) per study / per pathology, each error type of a study being the mean over its records; avg [12] =
+ * {accuracy, precision, recall, f1} x {example, macro, micro}. Zero-denominator ratios: 0 in example / cls, NaN in the micro ratios. A row index
+ * or offset outside its table makes that study's outputs (and the sums it enters) NaN. workspace: (56 * S + 64) * 8 bytes, 8-byte aligned.
+ * Fixed summation order, no atomics: repeated launches are bit-identical. */
+int cxr_chexbert_scores(const long* pred, int n_pred, const long* ref, int n_ref, const int* pred_row, const int* ref_row, int M,
+                        const int* study_off, int S, double* example, double* cls, double* avg, void* workspace, long workspace_bytes,
+                        hipStream_t stream);
+
 /* ---- cached-decode step inputs in one launch (REF:modelling_longitudinal.py:251-295 prepare_inputs_for_generation and its single / multi
  * copies): from ids[r, strip:cur] -> new_id = last token, tt = token_ids_to_token_type_ids_past (:340-364; rows < half_rows use special0, the
  * rest special1), mask = ids != mask_token_id and pos = relu(cumsum(mask)-1)[-1] (:274-277; mask == NULL skips both); tt / pos are also written
