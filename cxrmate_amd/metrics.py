@@ -1,4 +1,4 @@
-"""Test-stage metrics on MI355X: `CXRBERT` (below) and `CheXbertClassificationMetrics` (its own docstring).
+"""Test-stage metrics on MI355X: `CXRBERT` (below), `CheXbertClassificationMetrics` and `COCONLGMetricsMIMICCXR` (their own docstrings).
 
 CXR-BERT similarity metric -- the evaluation-time consumer of the reward kernels (reference tools/metrics/cxr_bert.py:10-184).
 
@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import csv
 import os
+import re
 import time
 
 import numpy as np
@@ -252,3 +253,153 @@ class CheXbertClassificationMetrics:
         if self.accumulate_over_dicoms:
             score["num_dicom_ids"] = float(len(set(m["dicom_id"])))
         return score
+
+
+# ================================================================================================ COCO NLG metrics
+_NLG_DEVICE_COLUMNS = ("bleu_1", "bleu_2", "bleu_3", "bleu_4", "rouge", "cider")
+_NLG_ORDER = ("bleu", "meteor", "rouge", "cider", "spice")                   # the reference's column order (tools/metrics/coco.py:155-172)
+_NLG_HOST = ("meteor", "spice")                                             # Java scorers: only as injected objects
+
+
+def merge_report_parts(parts, accumulate_over_dicoms):
+    """The host step between gathering and scoring, as a pure function of the per-rank parts (rank order). A part is a dict of equally long lists:
+    `prediction`, `label` (one string per record), `study_id` and, when accumulating, `dicom_id`.
+    The reference fills dicts keyed by the DICOM id (by the study id when not accumulating) and drops duplicate rows from its table, so for a
+    repeated key the texts of the LAST record are scored, at the position and with the ids of the FIRST (tools/metrics/coco.py:123-147).
+    -> dict: `prediction`, `label`, `study_id`, `dicom_id` (lists, `dicom_id` None when not accumulating): the M scored records in order of first
+    appearance; `order` int64 [M]: those records grouped by study, the studies sorted by id when accumulating (pandas groupby) and in order of
+    first appearance otherwise; `studies`: the S ids in that order; `study_off` int32 [S + 1]: CSR offsets into `order`."""
+    pred = [t for p in parts for t in p["prediction"]]
+    label = [t for p in parts for t in p["label"]]
+    study = [_plain(v) for p in parts for v in p["study_id"]]
+    dicom = [_plain(v) for p in parts for v in p["dicom_id"]] if accumulate_over_dicoms else None
+    first, last = {}, {}
+    for i, k in enumerate(dicom if accumulate_over_dicoms else study):
+        first.setdefault(k, i)
+        last[k] = i
+    kept_study = [study[i] for i in first.values()]
+    rank = {}
+    for s in kept_study:
+        rank.setdefault(s, len(rank))
+    studies = sorted(rank) if accumulate_over_dicoms else list(rank)
+    rank = {s: r for r, s in enumerate(studies)}
+    group = np.array([rank[s] for s in kept_study], dtype=np.int64)
+    return {"prediction": [pred[last[k]] for k in first], "label": [label[last[k]] for k in first], "study_id": kept_study,
+            "dicom_id": [dicom[i] for i in first.values()] if accumulate_over_dicoms else None, "order": np.argsort(group, kind="stable"),
+            "studies": studies, "study_off": np.concatenate([[0], np.cumsum(np.bincount(group, minlength=len(studies)))]).astype(np.int32)}
+
+
+def stage_texts(predictions, labels):
+    """Scored texts -> the inputs of `ops.coco_nlg_scores` (int32 numpy arrays): every distinct text is staged once, words are interned into ids
+    with one dict, `ids_a` / `off_a` hold the `str.split()` tokens (BLEU, CIDEr) and `ids_b` / `off_b` the `str.split(" ")` tokens (ROUGE-L, for
+    which a leading or trailing blank is an empty token and a tab does not split); `pairs` [M, 2] names each record's two texts and `ref_mult`
+    counts the records whose reference a text is."""
+    texts, words = {}, {}
+    pairs = np.array([(texts.setdefault(p, len(texts)), texts.setdefault(l, len(texts))) for p, l in zip(predictions, labels)],
+                     dtype=np.int32).reshape(-1, 2)
+    out = {"pairs": pairs, "ref_mult": np.bincount(pairs[:, 1], minlength=len(texts)).astype(np.int32)}
+    for name, sep in (("a", None), ("b", " ")):
+        ids, off = [], [0]
+        for t in texts:
+            ids.extend(words.setdefault(w, len(words)) for w in t.split(sep))
+            off.append(len(ids))
+        out["ids_" + name], out["off_" + name] = np.array(ids, dtype=np.int32), np.array(off, dtype=np.int32)
+    return out
+
+
+class COCONLGMetricsMIMICCXR:
+    """COCO NLG metrics (reference tools/metrics/coco.py:18-196, the source of `val_<section>_nlg_*`): per-record BLEU-1..4, ROUGE-L and CIDEr-D,
+    averaged over the DICOMs of a study first when accumulating, then over the studies.
+
+    Behaviour kept from the reference's torchmetrics class: its arguments in its order, update / compute / reset, records of all ranks merged in rank
+    order, one row per DICOM / study (see `merge_report_parts` for which record's texts a repeated key keeps), one CSV under `<exp_dir>/nlg_scores`
+    written by rank 0, and the returned dict, key for key. How it is computed is this build's own: columnar state, every distinct text staged once
+    as word ids, and everything the COCO caption scorers and pandas compute is ONE `cxr_coco_nlg_scores` call (csrc/coco_nlg.hip) in float64.
+
+    `metrics=None` means ['bleu', 'cider', 'rouge'] (the reference's own default cannot be constructed). The PTB tokenizer, METEOR and SPICE are
+    Java programs and are only accepted as injected objects: `tokenizer=` with `tokenize({id: [{'caption': str}]}) -> {id: [str]}` when
+    `use_tokenizer=True`, and `extra_scorers={'meteor': obj}` with `obj.compute_score(gts, res) -> (score, per-record scores)`."""
+
+    def __init__(self, split, exp_dir, accumulate_over_dicoms, metrics=None, use_tokenizer=True, dist_sync_on_step=False, tokenizer=None,
+                 extra_scorers=None, device=None):
+        self.split, self.exp_dir = split, exp_dir
+        self.accumulate_over_dicoms = bool(accumulate_over_dicoms)
+        self.metrics = [m.lower() for m in (["bleu", "cider", "rouge"] if metrics is None else metrics)]
+        self.use_tokenizer, self.dist_sync_on_step, self.tokenizer = bool(use_tokenizer), dist_sync_on_step, tokenizer
+        self.extra_scorers = dict(extra_scorers or {})
+        unknown = [m for m in self.metrics if m not in _NLG_ORDER]
+        if unknown:
+            raise ValueError(f"unknown COCO NLG metrics {unknown}: choose from {list(_NLG_ORDER)}")
+        for m in _NLG_HOST:
+            if m in self.metrics and not hasattr(self.extra_scorers.get(m), "compute_score"):
+                raise ValueError(f"'{m}' is a Java scorer that is not built here: pass extra_scorers={{'{m}': obj}} with obj.compute_score(gts, res)")
+        self.device = torch.device(device) if device is not None else None
+        self.save_dir = os.path.join(self.exp_dir, "nlg_scores")
+        os.makedirs(self.save_dir, exist_ok=True)
+        self.reset()
+
+    # ------------------------------------------------------------------------------------------ state (CXRBERT's: same columns, checks and messages)
+    reset = CXRBERT.reset
+    reports = CXRBERT.reports
+    update = CXRBERT.update
+
+    # ------------------------------------------------------------------------------------------ scoring
+    def columns(self):
+        """The score columns in the reference's order, restricted to the metrics asked for."""
+        cols = []
+        for m in _NLG_ORDER:
+            if m in self.metrics:
+                cols += [f"bleu_{k}" for k in range(1, 5)] if m == "bleu" else [m]
+        return cols
+
+    def compute(self, epoch):
+        from . import ops
+        if self.use_tokenizer and self.tokenizer is None:
+            raise RuntimeError("COCONLGMetricsMIMICCXR(use_tokenizer=True) needs tokenizer=: an object with the PTBTokenizer interface, "
+                               "tokenize({id: [{'caption': str}]}) -> {id: [str]} (the Java tokenizer is not built here); or use_tokenizer=False")
+        for group in self._label:                               # one reference per record, as the reference's callers pass it
+            assert len(group) == 1
+        part = {"prediction": list(self._pred), "label": [group[0] for group in self._label], "study_id": list(self._study)}
+        if self.accumulate_over_dicoms:
+            part["dicom_id"] = list(self._dicom)
+        parts = [part]
+        if _is_dist():                                          # parts of all ranks, rank order (reference: all_gather_object of the row dicts)
+            parts = [None] * torch.distributed.get_world_size()
+            torch.distributed.all_gather_object(parts, part)
+        m = merge_report_parts(parts, self.accumulate_over_dicoms)
+        keys = m["dicom_id"] if self.accumulate_over_dicoms else m["study_id"]
+        preds = [re.sub(" +", " ", t) for t in m["prediction"]]
+        labels = [re.sub(" +", " ", t) for t in m["label"]]
+        if self.use_tokenizer:
+            tok_p = self.tokenizer.tokenize({k: [{"caption": t}] for k, t in zip(keys, preds)})
+            tok_l = self.tokenizer.tokenize({k: [{"caption": t}] for k, t in zip(keys, labels)})
+            preds, labels = [tok_p[k][0] for k in keys], [tok_l[k][0] for k in keys]
+        st = stage_texts(preds, labels)
+        dev = self.device if self.device is not None else torch.device("cuda")
+        up = {k: torch.from_numpy(v).to(dev) for k, v in st.items()}
+        scores, _, _, avg = ops.coco_nlg_scores(up["ids_a"], up["off_a"], up["ids_b"], up["off_b"], up["pairs"], up["ref_mult"],
+                                                torch.from_numpy(m["order"].astype(np.int32)).to(dev), torch.from_numpy(m["study_off"]).to(dev))
+        scores, avg = scores.cpu().numpy(), avg.cpu().numpy()
+        table, mean = {}, {}
+        for c in self.columns():
+            if c in _NLG_DEVICE_COLUMNS:
+                j = _NLG_DEVICE_COLUMNS.index(c)
+                table[c], mean[c] = scores[:, j], float(avg[j])
+            else:                                               # an injected host scorer: its per-record values join the same study grouping
+                gts, res = {k: [t] for k, t in zip(keys, labels)}, {k: [t] for k, t in zip(keys, preds)}
+                _, per = self.extra_scorers[c].compute_score(gts, res)
+                table[c] = np.asarray(per, dtype=np.float64).reshape(len(keys))
+                per_study = np.add.reduceat(table[c][m["order"]], m["study_off"][:-1]) / np.diff(m["study_off"]) if len(keys) else np.zeros(0)
+                mean[c] = float(per_study.mean()) if len(per_study) else float("nan")
+        if not _is_dist() or torch.distributed.get_rank() == 0:
+            id_cols = ([("dicom_id", m["dicom_id"])] if self.accumulate_over_dicoms else []) + [("study_id", m["study_id"])]
+            path = os.path.join(self.save_dir, f'{self.split}_epoch-{epoch}_{time.strftime("%d-%m-%Y_%H-%M-%S")}.csv')
+            with open(path, "w", newline="") as f:
+                w = csv.writer(f)
+                w.writerow([n for n, _ in id_cols] + list(table))
+                w.writerows(zip(*(v for _, v in id_cols), *(v.tolist() for v in table.values())))
+        out = {"num_study_ids": float(len(m["studies"]))}
+        if self.accumulate_over_dicoms:
+            out["num_dicom_ids"] = float(len(set(m["dicom_id"])))
+        out.update(mean)
+        return out

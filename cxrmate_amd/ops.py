@@ -1663,3 +1663,44 @@ def chexbert_scores(pred, ref, pred_row, ref_row, study_off):
     LIB.call("cxr_chexbert_scores", _p(pred), pred.shape[0], _p(ref), ref.shape[0], _p(pred_row), _p(ref_row), M, _p(study_off), S, _p(example),
              _p(cls), _p(avg), _p(ws), ws.numel() * 8, _s())
     return example, cls, avg
+
+
+COCO_NLG_MAX_LEN = 8192
+
+
+def coco_nlg_workspace_bytes(n_ids_a, M):
+    """Bytes of workspace cxr_coco_nlg_scores needs for a split() stream of `n_ids_a` tokens and `M` records (the formula in its header comment)."""
+    cap = 1024
+    while cap < 2 * n_ids_a:
+        cap <<= 1
+    return cap * 12 + 3 * ((n_ids_a * 4 + 7) // 8 * 8) + 32 * M
+
+
+def coco_nlg_scores(ids_a, off_a, ids_b, off_b, pairs, ref_mult, order, study_off):
+    """COCO NLG scores on word ids (see cxr_coco_nlg_scores). ids_a / off_a: the str.split() tokens of every distinct text as a CSR stream, ids_b /
+    off_b: its str.split(" ") tokens (int32, off_* [n_texts + 1]); pairs int32 [M, 2] (hypothesis text, reference text); ref_mult int32 [n_texts];
+    order int32 [M] (records grouped by study); study_off int32 [S + 1] -> float64 scores [M, 6] (bleu_1..4, rouge, cider), int32 ints [M, 9]
+    (len_hyp, len_ref, c_1..c_4, lcs, ROUGE len_hyp, len_ref), float64 study [S, 6] and avg [6]. A text longer than 8192 tokens raises ValueError."""
+    for t in (ids_a, off_a, ids_b, off_b, ref_mult, order, study_off):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous()
+    assert off_a.shape == off_b.shape and off_a.shape[0] >= 1 and study_off.shape[0] >= 1
+    n_texts, M, S = off_a.shape[0] - 1, pairs.shape[0], study_off.shape[0] - 1
+    assert ref_mult.shape == (n_texts,) and order.shape == (M,)
+    if not ids_a.is_cuda:
+        raise CxrError("coco_nlg_scores runs on the device: host tensors are refused (cxrmate_amd has no CPU / PyTorch fallback)")
+    for t in (off_a, ids_b, off_b, pairs, ref_mult, order, study_off):
+        assert t.device == ids_a.device
+    if n_texts:
+        longest = int(torch.maximum((off_a[1:] - off_a[:-1]).max(), (off_b[1:] - off_b[:-1]).max()))
+        if longest > COCO_NLG_MAX_LEN:
+            raise ValueError(f"coco_nlg_scores: a text of {longest} tokens exceeds the supported {COCO_NLG_MAX_LEN}")
+    dev = ids_a.device
+    scores = torch.empty((M, 6), dtype=torch.float64, device=dev)
+    ints = torch.empty((M, 9), dtype=torch.int32, device=dev)
+    study = torch.empty((S, 6), dtype=torch.float64, device=dev)
+    avg = torch.empty((6,), dtype=torch.float64, device=dev)
+    ws = torch.empty((coco_nlg_workspace_bytes(ids_a.shape[0], M) // 8,), dtype=torch.float64, device=dev)
+    LIB.call("cxr_coco_nlg_scores", _p(ids_a), ids_a.shape[0], _p(off_a), _p(ids_b), ids_b.shape[0], _p(off_b), n_texts, _p(pairs), _p(ref_mult),
+             M, _p(order), _p(study_off), S, _p(scores), _p(ints), _p(study), _p(avg), _p(ws), ws.numel() * 8, _s())
+    return scores, ints, study, avg

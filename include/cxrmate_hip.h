@@ -489,6 +489,22 @@ int cxr_chexbert_scores(const long* pred, int n_pred, const long* ref, int n_ref
                         const int* study_off, int S, double* example, double* cls, double* avg, void* workspace, long workspace_bytes,
                         hipStream_t stream);
 
+/* ---- COCO NLG scores (REF:tools/metrics/coco.py:106-196 over pycocoevalcap's bleu_scorer / rouge / cider_scorer, one reference per record) on
+ * integer word ids, float64 throughout. Every distinct text is staged once as two CSR token streams over the same n_texts texts: ids_a / off_a its
+ * str.split() tokens (BLEU, CIDEr-D), ids_b / off_b its str.split(" ") tokens (ROUGE-L); off_* int32 [n_texts+1], starting at 0. pairs int32
+ * [M][2] = (hypothesis text, reference text) of every scored record; ref_mult int32 [n_texts] = the number of scored records whose reference is
+ * that text (its weight in CIDEr's document frequency); order int32 [M] = the records grouped by study, study_off int32 [S+1] = CSR offsets into
+ * it. -> scores [M][6] = bleu_1..4, rouge, cider; ints int32 [M][9] = len_hyp, len_ref, clipped 1..4-gram matches, lcs, the two ROUGE lengths;
+ * study [S][6] = mean over a study's records; avg [6] = mean over the studies. N-gram identity is exact for any int32 vocabulary; every
+ * floating-point sum has a fixed order and there are no floating-point atomics, so repeated launches are bit-identical. A text longer than 8192
+ * tokens, malformed offsets or a short workspace return -1 before anything is launched (the offsets are checked on the host: the call waits for
+ * the stream once). A record with a text index outside [0, n_texts) gets NaN scores and -1 integers; a study with offsets or record indices
+ * outside their arrays gets NaN. M == 0 and S == 0 are accepted (avg is then NaN). workspace: cap * 12 + 3 * round_up(4 * n_ids_a, 8) + 32 * M
+ * bytes, cap = the power of two >= max(1024, 2 * n_ids_a); 8-byte aligned. */
+int cxr_coco_nlg_scores(const int* ids_a, long n_ids_a, const int* off_a, const int* ids_b, long n_ids_b, const int* off_b, int n_texts,
+                        const int* pairs, const int* ref_mult, int M, const int* order, const int* study_off, int S, double* scores, int* ints,
+                        double* study, double* avg, void* workspace, long workspace_bytes, hipStream_t stream);
+
 /* ---- cached-decode step inputs in one launch (REF:modelling_longitudinal.py:251-295 prepare_inputs_for_generation and its single / multi
  * copies): from ids[r, strip:cur] -> new_id = last token, tt = token_ids_to_token_type_ids_past (:340-364; rows < half_rows use special0, the
  * rest special1), mask = ids != mask_token_id and pos = relu(cumsum(mask)-1)[-1] (:274-277; mask == NULL skips both); tt / pos are also written
