@@ -1,4 +1,5 @@
 // Backward of the fused attention (head_dim 64, bf16, fp32 accumulate): dQ, dK, dV with P recomputed from (Q, K, LSE).
+// A query row WITHOUT a visible key (forward: uniform over all keys) gets p = 0 here and contributes nothing to dQ, dK, dV: such rows never reach the loss.
 // Two deterministic kernels (no atomics):
 //   dkdv: workgroup = 128 keys (32 per wave, key on the MFMA lane) sweeping 64-query tiles; S and dP accumulators are
 //         already the B operands of dV^T += dO^T.P and dK^T += Q^T.dS (accumulator-as-operand); dK/dV never leave registers.

@@ -524,7 +524,8 @@ def _drop_args(drop):
 
 
 def attention_bwd(q, k, v, o, do, lse, heads, scale, kpm=None, causal=False, causal_shift=None, drop=None, dk_out=None, dv_out=None, dq_out=None):
-    """dq_out / dk_out / dv_out: optional pre-allocated [B,T,D] views (column slices of one wider matrix); dk_out and dv_out must have EQUAL strides."""
+    """dq_out / dk_out / dv_out: optional pre-allocated [B,T,D] views (column slices of one wider matrix); dk_out and dv_out must have EQUAL strides.
+    A query row without a visible key (the forward attends uniformly there) contributes nothing to dq, dk, dv: such rows never reach the loss."""
     B, Tq, D = q.shape
     Tk = k.shape[1]
     dq = dq_out if dq_out is not None else torch.empty((B, Tq, D), device=q.device, dtype=BF16)
