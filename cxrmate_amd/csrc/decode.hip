@@ -75,7 +75,7 @@ extern "C" int cxr_topk_rows(const float* x, long ld, long R, int n, int K, floa
 
 // ------------------------------------------------------------------------------------------------------------------
 // Device-side beam search (reference: generate(num_beams=4) -> TF5 generation/utils.py:3208-3560 `_beam_search`, do_sample=False,
-// early_stopping=False, one EOS id, num_return_sequences=1). One launch per decode step does what the host loop of the library does with
+// one EOS id; early_stopping False through cxr_beam_step / _lp / _idx, True and "never" through cxr_beam_step_es). One launch per decode step does what the host loop of the library does with
 // ~40 small tensor ops and two host synchronisations: log-softmax of the study's beams + running scores, the 2*beams best continuations,
 // the split into running / finished beams, the merge into the finished set, the improvement test, and the row indices the KV cache is
 // reordered by. Rows are BEAM-MAJOR (row = beam * B + study): the beams of a study then share its cross-attention K/V in the decode
@@ -95,7 +95,11 @@ struct BeamArgs {
     long eos;
     float div;                             // (cur + 1 - prompt_len) ^ length_penalty
     int prenorm;                           // 1: `logits` are already (processed) log-probs, taken as they are (log-sum-exp fixed at 0)
-    int* run_bidx; int* fin_bidx;          // int32 [beams, B, L] beam-index histories (cxr_beam_step_idx only; null otherwise)
+    int* run_bidx; int* fin_bidx;          // int32 [beams, B, L] beam-index histories (cxr_beam_step_idx / _es; null otherwise)
+    // early stopping (cxr_beam_step_es; the other entry points pass div_run = div, es_true = 0, allfin = null: the early_stopping=False search)
+    float div_run;                         // divisor of the improvement test (TF5:gen:3044-3048): div, or (max_length - prompt_len) ^ length_penalty
+    int es_true;                           // early_stopping=True: a full finished set takes no more hypotheses; stop once every study's is full
+    int* allfin;                           // [2, B] by step parity: the study's finished set is full (es_true only; null otherwise)
 };
 constexpr int BEAM_CHUNK = 4096;           // vocabulary entries per scan workgroup (16 per thread, held in registers)
 
@@ -103,7 +107,13 @@ __device__ __forceinline__ bool beam_stopped(const BeamArgs& a) {
     const int* unsat_prev = a.unsat + (a.par ^ 1) * a.B; const int* hit_prev = a.allhit + (a.par ^ 1) * a.B;
     int any_unsat = 0, all_hit = 1;
     for (int i = 0; i < a.B; ++i) { any_unsat |= unsat_prev[i]; all_hit &= hit_prev[i]; }
-    return !(any_unsat && !all_hit);
+    int all_fin = 0;                       // TF5:gen:3069: every finished slot of EVERY study is filled (early_stopping=True only)
+    if (a.es_true) {
+        const int* fin_prev = a.allfin + (a.par ^ 1) * a.B;
+        all_fin = 1;
+        for (int i = 0; i < a.B; ++i) all_fin &= fin_prev[i];
+    }
+    return !(any_unsat && !all_fin && !all_hit);
 }
 
 // Scan: workgroup (chunk, row) reduces its slice of the row's logits to (max, sum exp(x - max)) and its K2 largest entries (descending, ties ->
@@ -184,7 +194,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
     __syncthreads();
     if (s_stop) {                           // frozen: identity reorder, flags carried over
         if (tid < NB) a.beam_idx[tid * B + b] = tid * B + b;
-        if (tid == 0) { unsat_new[b] = unsat_prev[b]; hit_new[b] = hit_prev[b]; }
+        if (tid == 0) {
+            unsat_new[b] = unsat_prev[b]; hit_new[b] = hit_prev[b];
+            if (a.es_true) a.allfin[a.par * B + b] = a.allfin[(a.par ^ 1) * B + b];
+        }
         return;
     }
     // ---- log-softmax offsets of the study's beams from the chunk partials: lp = x - (max + log(sum exp(x - max)) - running score)
@@ -234,6 +247,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
         const float NEG = -1.0e9f;
         float run_lp[K2], fin_lp[K2]; bool hits[K2]; bool all_hits = true;
         const bool unsat = unsat_prev[b] != 0;
+        bool full = a.es_true != 0;                        // TF5:gen:3184-3185: the finished set as it was BEFORE this step is full
+        for (int i = 0; i < NB && full; ++i) full = a.finished[b * NB + i] != 0;
         for (int j = 0; j < K2; ++j) {
             c_beam[j] = c_idx[j] / V; c_tok[j] = c_idx[j] % V;
             hits[j] = (c_tok[j] == (int)a.eos) || (a.cur + 1 >= a.max_length);
@@ -241,6 +256,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
             run_lp[j] = c_lp[j] + (hits[j] ? NEG : -0.0f);
             const bool just = hits[j] && j < NB;
             fin_lp[j] = c_lp[j] / a.div;
+            fin_lp[j] = fin_lp[j] + (full ? NEG : -0.0f);
             fin_lp[j] = fin_lp[j] + (unsat ? -0.0f : NEG);
             fin_lp[j] = fin_lp[j] + (just ? -0.0f : NEG);
         }
@@ -265,7 +281,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
         }
         float mn = nsc[0];
         for (int i = 1; i < NB; ++i) mn = fminf(mn, nsc[i]);
-        const float best_run = new_run[0] / a.div;      // the library divides by (cur - prompt)^lp AFTER its cur += 1: the same number
+        const float best_run = new_run[0] / a.div_run;  // the library divides by (cur - prompt)^lp AFTER its cur += 1: the same number as div
         bool improve = false;
         for (int i = 0; i < NB; ++i) improve = improve || (best_run > (nfin[i] ? mn : NEG));
         for (int i = 0; i < NB; ++i) {
@@ -274,6 +290,11 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
         }
         unsat_new[b] = (unsat && improve) ? 1 : 0;
         hit_new[b] = all_hits ? 1 : 0;
+        if (a.es_true) {
+            bool all_fin = true;
+            for (int i = 0; i < NB; ++i) all_fin = all_fin && nfin[i];
+            a.allfin[a.par * B + b] = all_fin ? 1 : 0;
+        }
     }
     __syncthreads();
     // ---- token rows: column t of every beam of the study is read, then written, by one thread (in place)
@@ -326,13 +347,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamArgs a) {
 // fp32 as its tensor division does. ws: beams*B * ceil(V / 4096) * (2 + 4*beams) floats.
 static int beam_step_launch(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
                             unsigned char* finished, int* unsat, int* allhit, long* beam_idx, float* ws, int B, int nb, int V, int L, int cur,
-                            int max_length, long eos, float div, int prenorm, int* run_bidx, int* fin_bidx, hipStream_t stream) {
+                            int max_length, long eos, float div, int prenorm, int* run_bidx, int* fin_bidx, hipStream_t stream,
+                            float div_run = 0.f, int es_mode = 0, int* allfin = nullptr) {
     if (B <= 0 || V <= 0 || cur < 0 || cur >= L || (nb != 1 && nb != 2 && nb != 3 && nb != 4 && nb != 5 && nb != 8) || (long)nb * V >= (1L << 31) || !ws)
         return CXR_ERR_ARG;
     const int nch = cdiv(V, BEAM_CHUNK);
     if (nch > 32 || (run_bidx == nullptr) != (fin_bidx == nullptr)) return CXR_ERR_ARG;
+    if (es_mode < 0 || es_mode > 2 || (es_mode == 1 && !allfin) || (es_mode == 2 && !(div_run > 0.f))) return CXR_ERR_ARG;
     BeamArgs a{logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur, max_length, cur & 1,
-               nch, eos, div, prenorm, run_bidx, fin_bidx};
+               nch, eos, div, prenorm, run_bidx, fin_bidx, es_mode == 2 ? div_run : div, es_mode == 1 ? 1 : 0, es_mode == 1 ? allfin : nullptr};
     const dim3 sg(nch, nb * B);
     const bool bidx = run_bidx != nullptr;
 #define BEAM_CASE(NB_) case NB_: CXR_LAUNCH(beam_scan_kernel<2 * NB_>, sg, dim3(256), 0, stream, a);                       \
@@ -365,6 +388,19 @@ extern "C" int cxr_beam_step_idx(const float* logits, long ld, long* running, lo
     if (!run_bidx || !fin_bidx) return CXR_ERR_ARG;
     return beam_step_launch(logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
                             max_length, eos, div, logprobs ? 1 : 0, run_bidx, fin_bidx, stream);
+}
+
+// Any of the steps above with early_stopping (TF5:gen _check_early_stop_heuristic :3008, _beam_search_has_unfinished_sequences :3055,
+// _update_finished_beams :3150-3204). mode 0 = False (the search of the entry points above), 1 = True: a study whose finished set is full takes
+// no more hypotheses, and the search stops once every study's is (allfin int32 [2, B], double-buffered by the parity of `cur` like unsat / allhit,
+// 0 at the start), 2 = "never": the improvement test divides by div_run = (max_length - prompt_len) ** length_penalty (the caller passes it when
+// length_penalty > 0, else div). run_bidx / fin_bidx may both be null.
+extern "C" int cxr_beam_step_es(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores,
+                                unsigned char* finished, int* unsat, int* allhit, int* allfin, long* beam_idx, float* ws, int* run_bidx,
+                                int* fin_bidx, int B, int nb, int V, int L, int cur, int max_length, long eos, float div, float div_run,
+                                int early_stopping, int logprobs, hipStream_t stream) {
+    return beam_step_launch(logits, ld, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, ws, B, nb, V, L, cur,
+                            max_length, eos, div, logprobs ? 1 : 0, run_bidx, fin_bidx, stream, div_run, early_stopping, allfin);
 }
 
 // The KV-cache reorder of a beam step for ALL layers in one launch: out[i][r, :rows, :] = in[i][idx[r], :rows, :] for up to 16 tensors of

@@ -10,9 +10,161 @@ the sampled sequence is re-scored by ONE teacher-forced pass whose per-step inpu
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
+
+
+class _Unset:
+    """Signature default of the generate() options a `generation_config` object may supply: tells "not passed" from "passed the default"."""
+
+    def __repr__(self):
+        return "<unset>"
+
+
+UNSET = _Unset()
+
+# options of generate() a `generation_config` object may supply, with the engine's defaults (the effective values of a call that passes neither)
+GENERATION_DEFAULTS = dict(
+    max_length=None, max_new_tokens=None, bos_token_id=None, eos_token_id=None, pad_token_id=None, num_beams=1, do_sample=False, top_k=50, top_p=1.0,
+    temperature=1.0, output_scores=False, return_dict_in_generate=False, use_cache=True, length_penalty=1.0, repetition_penalty=1.0,
+    no_repeat_ngram_size=0, min_length=0, min_new_tokens=None, num_return_sequences=1, output_logits=False, bad_words_ids=None, suppress_tokens=None,
+    begin_suppress_tokens=None, sequence_bias=None, forced_bos_token_id=None, forced_eos_token_id=None, early_stopping=False)
+
+# fields of a `generation_config` object this engine cannot honour -> is the value neutral (the field then changes nothing in the library either)?
+_UNSUPPORTED_FIELDS = {
+    "num_beam_groups": lambda v: v <= 1, "diversity_penalty": lambda v: v == 0.0, "penalty_alpha": lambda v: v == 0.0, "typical_p": lambda v: v >= 1.0,
+    "min_p": lambda v: False, "top_h": lambda v: False, "epsilon_cutoff": lambda v: v <= 0.0, "eta_cutoff": lambda v: v <= 0.0,
+    "exponential_decay_length_penalty": lambda v: False, "encoder_repetition_penalty": lambda v: v == 1.0,
+    "encoder_no_repeat_ngram_size": lambda v: v <= 0, "guidance_scale": lambda v: v == 1.0, "renormalize_logits": lambda v: v is False,
+    "remove_invalid_values": lambda v: v is False, "constraints": lambda v: False, "force_words_ids": lambda v: False,
+    "dola_layers": lambda v: False, "stop_strings": lambda v: False, "max_time": lambda v: False, "watermarking_config": lambda v: False,
+    "prompt_lookup_num_tokens": lambda v: False}
+
+
+def resolve_generation_options(kwargs, generation_config=None):
+    """The effective options of one generate() call (pure host code). kwargs: the options the caller PASSED (an option left out, or given as UNSET,
+    was not passed); generation_config: any object with attributes (transformers.GenerationConfig is the intended one), or None. Precedence: a
+    keyword the caller passed wins, even when it equals the default; otherwise a non-None field of the object applies; otherwise the engine's
+    default (GENERATION_DEFAULTS). A field of the OBJECT this engine cannot honour, set to a non-neutral value, raises NotImplementedError naming
+    it (the same names passed as plain keywords stay ignored). -> dict with every key of GENERATION_DEFAULTS."""
+    out = {}
+    for name, default in GENERATION_DEFAULTS.items():
+        if name in kwargs and kwargs[name] is not UNSET:
+            out[name] = kwargs[name]
+            continue
+        field = getattr(generation_config, name, None) if generation_config is not None else None
+        out[name] = default if field is None else field
+    if generation_config is not None:
+        for name, neutral in _UNSUPPORTED_FIELDS.items():
+            v = getattr(generation_config, name, None)
+            if v is not None and not neutral(v):
+                raise NotImplementedError(f"generation_config.{name} = {v!r} is not supported by this engine")
+        beams = out["num_beams"]
+        if out["do_sample"] and beams is not None and int(beams) > 1:
+            raise NotImplementedError("generation_config: do_sample with num_beams > 1 (beam sampling) is not supported by this engine")
+        eos = out["eos_token_id"]
+        if isinstance(eos, (list, tuple)) and not ("eos_token_id" in kwargs and kwargs["eos_token_id"] is not UNSET):
+            if len(eos) != 1:
+                raise NotImplementedError(f"generation_config.eos_token_id = {eos!r}: this engine stops on one EOS id")
+            out["eos_token_id"] = eos[0]
+    return out
+
+
+def _is_id(t):
+    return isinstance(t, (int, np.integer))
+
+
+def token_constraints(vocab_size, eos_token_id, prompt_len, max_length, sequence_bias=None, bad_words_ids=None, suppress_tokens=None,
+                      begin_suppress_tokens=None, forced_bos_token_id=None, forced_eos_token_id=None):
+    """Validates the token-constraint options as the library's processors do (TF5 logits_process.py SequenceBiasLogitsProcessor._validate_arguments
+    :1351, NoBadWordsLogitsProcessor :1450-1481, same messages) and -> a hashable description of them, or None when none is set:
+    (sequence_bias entries ((ids, bias), ...) in the caller's order, bad words (ids, ...) without single [eos] entries, forced_bos id | None,
+    forced_eos ids, suppress ids, begin_suppress ids, max_length, begin_index). prompt_len counts the prepended BOS. An id >= vocab_size in
+    sequence_bias / bad_words_ids raises the library's ValueError here, before decoding (the library raises it at the first step); a forced id
+    outside the vocabulary (an IndexError of the library's first forced step) is a ValueError too."""
+    if all(o is None for o in (sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, forced_bos_token_id, forced_eos_token_id)):
+        return None
+
+    def seq_table(table):                                    # the library's dict: a repeated key keeps its first position and its last bias
+        if not isinstance(table, dict) and not isinstance(table, list) or len(table) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {table}.")
+        if isinstance(table, dict) and any(not isinstance(k, tuple) for k in table):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {table}.")
+        if isinstance(table, dict) and any(any((not _is_id(t) or t < 0) for t in k) or len(k) == 0 for k in table):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {table}.")
+
+        def pair_ok(e):
+            return (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], list) and len(e[0]) > 0
+                    and all(_is_id(t) and t > 0 for t in e[0]) and isinstance(e[1], float))
+        if isinstance(table, list) and any(not pair_ok(e) for e in table):
+            raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, but is {table}.")
+        if isinstance(table, dict) and any(not isinstance(b, float) for b in table.values()):
+            raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {table}.")
+        d = dict(table) if isinstance(table, dict) else {tuple(e[0]): e[1] for e in table}
+        invalid = [int(t) for k in d for t in k if t >= vocab_size]
+        if invalid:
+            raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {invalid}")
+        return tuple((tuple(int(t) for t in k), float(b)) for k, b in d.items())
+
+    bias = seq_table(sequence_bias) if sequence_bias is not None else ()
+    bad = ()
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+        if any(not isinstance(w, list) for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids}.")
+        if any(any((not _is_id(t) or t < 0) for t in w) for w in bad_words_ids):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+        words = [w for w in bad_words_ids if eos_token_id is None or w != [eos_token_id]]      # TF5 :1454-1464
+        bad = tuple(k for k, _ in seq_table({tuple(w): float("-inf") for w in words}))
+
+    def id_list(name, v, one_ok=False):
+        if v is None:
+            return ()
+        if one_ok and _is_id(v):
+            v = [v]
+        if hasattr(v, "tolist"):
+            v = v.tolist()
+        if not isinstance(v, (list, tuple)) or any(not _is_id(t) or t < 0 for t in v):
+            raise ValueError(f"`{name}` has to be a list of non-negative integers, but is {v}.")
+        return tuple(int(t) for t in v)
+    feos = id_list("forced_eos_token_id", forced_eos_token_id, one_ok=True)
+    fbos = id_list("forced_bos_token_id", forced_bos_token_id, one_ok=True)
+    if len(fbos) > 1:
+        raise ValueError(f"`forced_bos_token_id` has to be one id, but is {forced_bos_token_id}.")
+    out_of_range = [t for t in fbos + feos if t >= vocab_size]
+    if out_of_range:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being forced: {out_of_range}")
+    begin_index = prompt_len + (1 if (prompt_len <= 1 and fbos) else 0)                       # TF5 generation/utils.py:1278-1283
+    return (bias, bad, fbos[0] if fbos else None, feos, id_list("suppress_tokens", suppress_tokens),
+            id_list("begin_suppress_tokens", begin_suppress_tokens), int(max_length), int(begin_index))
+
+
+def constraint_tables(cons, device):
+    bias, bad, fbos, feos, suppress, begin, max_length, begin_index = cons
+    return ops.ConstraintTables(device, bias, bad, fbos, feos, suppress, begin, max_length, begin_index)
+
+
+def process_scores_(scores, ids, cur, eos, procs, tables=None):
+    """The processors of one step, one launch: procs = (repetition penalty, n-gram size, absolute min length) -> cxr_logits_process_f32;
+    procs = (..., token constraints) -> cxr_logits_constrain_f32 over the constraints' device tables."""
+    if len(procs) == 3:
+        return ops.logits_process_(scores, ids, cur, eos, *procs)
+    return ops.logits_constrain_(scores, ids, cur, eos, *procs[:3], tables=tables)
+
+
+def early_stopping_mode(early_stopping, length_penalty):
+    """early_stopping of generate() -> 0 (False), 1 (True), 2 ("never" with a positive length penalty: the only case in which "never" differs
+    from False, TF5 generation/utils.py:3044-3048). Anything else raises the library's ValueError (configuration_utils.py:667)."""
+    if early_stopping is None or early_stopping is False:
+        return 0
+    if early_stopping is True:
+        return 1
+    if isinstance(early_stopping, str) and early_stopping == "never":
+        return 2 if float(length_penalty) > 0.0 else 0
+    raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}.")
 
 
 class DecodeSession:
@@ -66,13 +218,24 @@ class DecodeSession:
         self.fills = 0                                     # number of reset()s = prefills: every one overwrites the cross K / V (decoder.SharedCrossKV)
         self.beam = None                                   # device-side beam-search state (beam_state)
         self.rec_bufs = {}                                 # per-step outputs of generate (output_logits / output_scores): [Lmax, rows, V] fp32 each
+        self.cons = {}                                     # token constraints (hashable description) -> their device tables (constraint_tables)
         self._cache_home = (list(self.cache.k), list(self.cache.v), list(self.cache.k2), list(self.cache.v2))
 
-    def beam_state(self, nb, pad, bidx=False):
+    def constraint_tables(self, cons):
+        """Device tables of the token constraints `cons`, owned by the session: step graphs bake their addresses, so a table lives as long as the
+        graphs keyed by it (the `mode` key of a step carries `cons`). Built outside any capture; a ninth description drops the tables AND the graphs."""
+        if cons not in self.cons:
+            if len(self.cons) >= 8:
+                self.cons.clear()
+                self.graphs.clear()
+            self.cons[cons] = constraint_tables(cons, self.ids.device)
+        return self.cons[cons]
+
+    def beam_state(self, nb, pad, bidx=False, allfin=False):
         """State of a device-side beam search over this session's rows (BEAM-MAJOR: row = beam * studies + study, so the beams of a study
         share its cross-attention K/V): `self.ids` viewed [nb, B, Lmax] holds the running beams; finished beams, scores and the stop flags
         live here (csrc/decode.hip beam_step_kernel). bidx: also the beam-index histories of the running and finished beams (int32 [nb, B, Lmax],
-        -1 = no token chosen), allocated on first use."""
+        -1 = no token chosen), allocated on first use. allfin: also the "finished set is full" flags of early_stopping=True (int32 [2, B])."""
         dev, B = self.ids.device, self.B // nb
         if self.beam is None or self.beam["nb"] != nb:
             self.beam = dict(nb=nb, sequences=torch.zeros((nb, B, self.Lmax), dtype=torch.int64, device=dev),
@@ -92,6 +255,10 @@ class DecodeSession:
                 st["run_bidx"] = torch.empty((nb, B, self.Lmax), dtype=torch.int32, device=dev)
                 st["fin_bidx"] = torch.empty((nb, B, self.Lmax), dtype=torch.int32, device=dev)
             st["run_bidx"].fill_(-1); st["fin_bidx"].fill_(-1)
+        if allfin:
+            if "allfin" not in st:
+                st["allfin"] = torch.empty((2, B), dtype=torch.int32, device=dev)
+            st["allfin"].zero_()
         return st
 
     def record_buffers(self, logits, scores):
@@ -135,7 +302,8 @@ class DecodeSession:
 
     def step(self, cur, strip, mode, n=1):
         """Append tokens cur .. cur+n-1 (0-based columns of self.ids). mode = (kind, special_token_ids, mask_token_id, top_k, temperature, eos, pad,
-        train, top_p, procs, rec); procs = (repetition penalty, n-gram size, absolute min length) of the generation controls, or None; rec =
+        train, top_p, procs, rec); procs = (repetition penalty, n-gram size, absolute min length[, token constraints]) of the generation controls,
+        or None (the constraints' tables: constraint_tables, built before the first step); rec =
         (record logits, record scores, row groups nb of the study-major permutation) of output_logits / output_scores, or None. The n cached
         steps are ONE hipGraph (a replay costs ~9 us of launch overhead whatever it holds: per token at n = 1, per 8 tokens at n = 8)."""
         prefill = self.cache.len == 0
@@ -172,6 +340,7 @@ class DecodeSession:
         # per-step outputs (csrc/gen_record.hip): raw logits before any processor, scores as TF5 stores them; slot `cur` of the session's buffers
         lo, so = self.record_buffers(rec[0], rec[1]) if rec is not None else (None, None)
         lo, so = None if lo is None else lo[cur], None if so is None else so[cur]
+        tables = self.cons[procs[3]] if procs is not None and len(procs) > 3 else None
         if prefill:
             fed = self.ids[:, strip:cur]
             new, mask, tt, pos = m._step_inputs(fed, special, mask_token_id, prefill=True)
@@ -198,7 +367,7 @@ class DecodeSession:
         if new is not None:
             logits = m._dec.decode(self.cache, new, self.enc16, self.enc_mask8, mask, tt, pos, train=train, seed=self.seed)
         if kind == "beam":                                          # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
-            nb, penalty, (prompt_len, max_length) = top_k, temperature, top_p
+            nb, penalty, (prompt_len, max_length, es) = top_k, temperature, top_p
             st, c = self.beam, self.cache
             if procs is None and (lo is not None or so is not None):  # scores = log_softmax(logits) (TF5:gen:3387, :3396), study-major rows
                 ops.gen_record(logits, lo, so, log_softmax=True, nb=nb)
@@ -206,13 +375,14 @@ class DecodeSession:
                 if lo is not None:
                     ops.gen_record(logits, lo, nb=nb)
                 ops.log_softmax_rows_(logits)
-                ops.logits_process_(logits, self.ids, cur, -1 if eos is None else eos, *procs)
+                process_scores_(logits, self.ids, cur, -1 if eos is None else eos, procs, tables)
                 if so is not None:
                     ops.gen_record(logits, None, so, nb=nb)
             ops.beam_step(logits, self.ids.view(nb, self.B // nb, self.Lmax), st["sequences"], st["run_scores"], st["beam_scores"], st["finished"],
                           st["unsat"], st["allhit"], st["beam_idx"], cur, max_length, -1 if eos is None else eos,
                           float(cur + 1 - prompt_len) ** penalty, ws=st["ws"], logprobs=procs is not None,
-                          bidx=(st["run_bidx"], st["fin_bidx"]) if rec is not None else None)
+                          bidx=(st["run_bidx"], st["fin_bidx"]) if rec is not None else None,
+                          early=None if not es else (es, float(max_length - prompt_len) ** penalty if es == 2 else 0.0, st.get("allfin")))
             ops.gather_batch_multi(c.k + c.v, st["beam_idx"], c.len, c.k2 + c.v2)
             self._swap_caches()
             self.last_tt = self.last_pos = None
@@ -227,7 +397,7 @@ class DecodeSession:
         if procs is not None:                                                   # processors before the warpers of select_token (TF5 order)
             if lo is not None:
                 ops.gen_record(logits, lo, nb=nperm)
-            ops.logits_process_(logits, self.ids, cur, eos_, *procs)
+            process_scores_(logits, self.ids, cur, eos_, procs, tables)
             if so is not None:
                 ops.gen_record(logits, None, so, nb=nperm)
         if n_smp:                                                               # one launch for sampled + greedy rows
@@ -280,12 +450,31 @@ class GenerationMixin:
 
     # ------------------------------------------------------------------------------------------ generate
     def _generate(self, inputs=None, pixel_values=None, encoder_outputs=None, decoder_input_ids=None, input_ids=None,
-                  special_token_ids=None, mask_token_id=None, max_length=None, max_new_tokens=None, bos_token_id=None,
-                  eos_token_id=None, pad_token_id=None, num_beams=1, do_sample=False, top_k=50, top_p=1.0, temperature=1.0,
-                  output_scores=False, return_dict_in_generate=False, use_cache=True, length_penalty=1.0, return_margins=False,
-                  forced_tokens=None, record_inputs=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=None,
-                  num_return_sequences=1, output_logits=False, **unused):
+                  special_token_ids=None, mask_token_id=None, max_length=UNSET, max_new_tokens=UNSET, bos_token_id=UNSET,
+                  eos_token_id=UNSET, pad_token_id=UNSET, num_beams=UNSET, do_sample=UNSET, top_k=UNSET, top_p=UNSET, temperature=UNSET,
+                  output_scores=UNSET, return_dict_in_generate=UNSET, use_cache=UNSET, length_penalty=UNSET, return_margins=False,
+                  forced_tokens=None, record_inputs=False, repetition_penalty=UNSET, no_repeat_ngram_size=UNSET, min_length=UNSET,
+                  min_new_tokens=UNSET, num_return_sequences=UNSET, output_logits=UNSET, bad_words_ids=UNSET, suppress_tokens=UNSET,
+                  begin_suppress_tokens=UNSET, sequence_bias=UNSET, forced_bos_token_id=UNSET, forced_eos_token_id=UNSET, early_stopping=UNSET,
+                  generation_config=None, **unused):
+        """Options left at UNSET take the non-None field of `generation_config` (any object with attributes), else the engine's default
+        (GENERATION_DEFAULTS, resolve_generation_options). Token constraints (bad_words_ids, suppress_tokens, begin_suppress_tokens, sequence_bias,
+        forced_bos_token_id, forced_eos_token_id) follow transformers 5.15.0's processors, in its order, in one launch per step
+        (csrc/logits_proc.hip); early_stopping is False, True or "never" (beam search)."""
         from .modelling import ModelOutput
+        passed = dict(max_length=max_length, max_new_tokens=max_new_tokens, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
+                      pad_token_id=pad_token_id, num_beams=num_beams, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                      output_scores=output_scores, return_dict_in_generate=return_dict_in_generate, use_cache=use_cache,
+                      length_penalty=length_penalty, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                      min_length=min_length, min_new_tokens=min_new_tokens, num_return_sequences=num_return_sequences, output_logits=output_logits,
+                      bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                      sequence_bias=sequence_bias, forced_bos_token_id=forced_bos_token_id, forced_eos_token_id=forced_eos_token_id,
+                      early_stopping=early_stopping)
+        o = resolve_generation_options(passed, generation_config)
+        (max_length, max_new_tokens, bos_token_id, eos_token_id, pad_token_id, num_beams, do_sample, top_k, top_p, temperature, output_scores,
+         return_dict_in_generate, use_cache, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens,
+         num_return_sequences, output_logits) = (o[k] for k in list(GENERATION_DEFAULTS)[:20])
+        es = early_stopping_mode(o["early_stopping"], 1.0 if length_penalty is None else length_penalty)
         if inputs is not None and pixel_values is None:
             pixel_values = inputs
         if special_token_ids is None:
@@ -331,12 +520,18 @@ class GenerationMixin:
         min_abs = (ids.shape[1] + int(min_new_tokens)) if min_new_tokens is not None else int(min_length or 0)
         min_abs = min_abs if (eos_token_id is not None and min_abs > ids.shape[1]) else 0
         procs = (penalty, ngram, min_abs) if (penalty != 1.0 or ngram > 0 or min_abs) else None
+        # token constraints (TF5 logits processors, validated as the library validates them): with any of them set, ONE launch of the constraint
+        # kernel applies them and the three controls above; with none, the launch (or no launch) of before
+        cons = token_constraints(self.config.decoder.vocab_size, eos_token_id, ids.shape[1], max_length, o["sequence_bias"], o["bad_words_ids"],
+                                 o["suppress_tokens"], o["begin_suppress_tokens"], o["forced_bos_token_id"], o["forced_eos_token_id"])
+        if cons is not None:
+            procs = (penalty, ngram, min_abs, cons)
         if procs is not None and max_length - 1 > ops.LOGITS_PROCESS_MAX_HIST:      # refused before decoding, not at the step that gets there
-            raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens take histories of at most "
-                             f"{ops.LOGITS_PROCESS_MAX_HIST} ids: max_length {max_length} is too long")
+            raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens and the token constraints take histories of "
+                             f"at most {ops.LOGITS_PROCESS_MAX_HIST} ids: max_length {max_length} is too long")
         if procs is not None and do_sample and output_scores:
-            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens together with do_sample=True and "
-                                      "output_scores=True are not supported: the differentiable scores are not processed")
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens / token constraints together with "
+                                      "do_sample=True and output_scores=True are not supported: the differentiable scores are not processed")
         enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
         enc_mask8 = None if enc_mask is None else enc_mask.to(device=dev, dtype=torch.uint8).contiguous()
         # per-step outputs (TF5 GenerateOutput fields): recorded only when the dict output asks for them
@@ -353,7 +548,7 @@ class GenerationMixin:
                 rec_out = {}
                 seqs, seq_scores = search(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams,
                                           bos_token_id, eos_token_id, pad_token_id, length_penalty, procs=procs, n_ret=n_ret,
-                                          record=record, rec_out=rec_out)
+                                          record=record, rec_out=rec_out, **({"es": es} if es else {}))
             if return_dict_in_generate:
                 out = ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None)
                 if want_scores:                                     # TF5 GenerateBeamEncoderDecoderOutput field order
@@ -454,6 +649,7 @@ class GenerationMixin:
         prompt_len = ids.shape[1]
         margins = []
         got = {"logits": [], "scores": []}
+        tables = constraint_tables(procs[3], dev) if procs is not None and len(procs) > 3 else None
         with torch.no_grad():
             cache = self._dec.new_cache(B, max_length, dev)
             unfinished = torch.ones(B, dtype=torch.int32, device=dev)
@@ -471,7 +667,7 @@ class GenerationMixin:
                 if record is not None and record[0]:
                     got["logits"].append(ops.gen_record(logits, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[0])
                 if procs is not None:                        # generation controls on the whole running history (BOS, prompt, generated)
-                    ops.logits_process_(logits, ids, ids.shape[1], -1 if eos_token_id is None else eos_token_id, *procs)
+                    process_scores_(logits, ids, ids.shape[1], -1 if eos_token_id is None else eos_token_id, procs, tables)
                 if record is not None and record[1]:
                     got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[1])
                 if forced_tokens is not None:
@@ -510,6 +706,8 @@ class GenerationMixin:
             ses.reset(ids, enc16, enc_mask8)
             if record is not None:                                   # before any step graph is captured (never from inside a capture)
                 ses.record_buffers(record[0], record[1])
+            if procs is not None and len(procs) > 3:
+                ses.constraint_tables(procs[3])
             if do_sample == "pair":
                 kind, special = "pair", (tuple(special_token_ids[0]), tuple(special_token_ids[1]))
             else:
@@ -694,8 +892,8 @@ class GenerationMixin:
 
     # ------------------------------------------------------------------------------------------ beam search
     def _beam_search_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                             procs=None, n_ret=1, record=None, rec_out=None):
-        """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False, early_stopping=False, num_return_sequences=1) over a DecodeSession:
+                             procs=None, n_ret=1, record=None, rec_out=None, es=0):
+        """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False; es: early_stopping as early_stopping_mode() numbers it) over a DecodeSession:
         beams*B rows decoded by the cached-step kernels (the beams of a study share its cross-attention K/V: ONE copy of the encoder rows, as in
         the SCST sample+greedy batch), the whole per-step bookkeeping in one kernel launch (ops.beam_step), the cache reorder in another, the
         steps replayed from hipGraphs eight at a time, and the stop condition polled asynchronously every 8 steps (the stopped state is frozen
@@ -712,10 +910,12 @@ class GenerationMixin:
             ses = self._session(B * nb, enc16.shape[1], max_length, enc_mask8 is not None, share=nb)
             ses.reset(ids.repeat(nb, 1), enc16, enc_mask8)
             ses.ids[:, prompt_len:] = pad
-            st = ses.beam_state(nb, pad, bidx=record is not None)
+            st = ses.beam_state(nb, pad, bidx=record is not None, allfin=es == 1)
             if record is not None:                                   # before any step graph is captured (never from inside a capture)
                 ses.record_buffers(record[0], record[1])
-            mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length),
+            if procs is not None and len(procs) > 3:
+                ses.constraint_tables(procs[3])
+            mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length, es),
                     procs, None if record is None else (record[0], record[1], nb))
             cur = prompt_len
             poll = None
@@ -729,7 +929,10 @@ class GenerationMixin:
                         if int(poll[0][0]) == 0:
                             break
                     par = (cur - 1) & 1                                     # flags of the last executed step (column cur - 1)
-                    going = ((st["unsat"][par].max() > 0) & (st["allhit"][par].min() == 0)).to(torch.int32).reshape(1)
+                    going = (st["unsat"][par].max() > 0) & (st["allhit"][par].min() == 0)
+                    if es == 1:                                             # early_stopping=True: every study's finished set is full
+                        going = going & (st["allfin"][par].min() == 0)
+                    going = going.to(torch.int32).reshape(1)
                     ses.poll_host.copy_(going, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record()
@@ -759,8 +962,9 @@ class GenerationMixin:
         return bidx[:, :int((bidx >= 0).sum(1).max())].clone()
 
     def _beam_search(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                     procs=None, n_ret=1, record=None, rec_out=None):
-        """TF5 generation/utils.py:3208-3560 with do_sample=False, early_stopping=False, one EOS id; the n_ret best hypotheses per study.
+                     procs=None, n_ret=1, record=None, rec_out=None, es=0):
+        """TF5 generation/utils.py:3208-3560 with do_sample=False, one EOS id, early_stopping False / True / "never" (es = 0 / 1 / 2,
+        early_stopping_mode()); the n_ret best hypotheses per study.
         record / rec_out as in _beam_search_session, with the beam-index histories kept by torch ops."""
         dev = ids.device
         B = ids.shape[0]
@@ -782,6 +986,7 @@ class GenerationMixin:
         batch_off = (torch.arange(B, device=dev) * nb).view(B, 1)
         cache = self._dec.new_cache(B * nb, max_length, dev)
         seed = self.next_dropout_seed() if self.training else None
+        tables = constraint_tables(procs[3], dev) if procs is not None and len(procs) > 3 else None
         if record is not None:                                     # beam-index histories (TF5:gen:3348-3351), absolute token columns
             run_bidx = torch.full((B, nb, max_length), -1, dtype=torch.int32, device=dev)
             fin_bidx = run_bidx.clone()
@@ -809,7 +1014,7 @@ class GenerationMixin:
                 ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
             else:                                                                             # processors act on the log-probs (TF5:gen:3388-3389)
                 ops.log_softmax_rows_(logits)
-                ops.logits_process_(logits, flat.contiguous(), cur, -1 if eos is None else eos, *procs)
+                process_scores_(logits, flat.contiguous(), cur, -1 if eos is None else eos, procs, tables)
                 if record is not None and record[1]:
                     got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device))[1])
                 logits.add_(run_scores.view(-1, 1))
@@ -828,6 +1033,8 @@ class GenerationMixin:
                 run_bidx = gather(topk_bidx, nxt)
             just = hits & top_mask[None, :]
             fin_lp = topk_lp / ((cur + 1 - prompt_len) ** length_penalty)
+            if es == 1:                                             # a full finished set takes no more hypotheses (TF5:gen:3184-3185)
+                fin_lp = fin_lp + finished.all(dim=1, keepdim=True).float() * -1.0e9
             fin_lp = fin_lp + (~unsat).float() * -1.0e9 + (~just).float() * -1.0e9
             m_seq = torch.cat((sequences, topk_seq), dim=1)
             m_sc = torch.cat((beam_scores, fin_lp), dim=1)
@@ -838,10 +1045,10 @@ class GenerationMixin:
                 fin_bidx = gather(torch.cat((fin_bidx, topk_bidx), dim=1), best)
             cache.reorder(beam_idx.contiguous())
             cur += 1
-            best_run = run_scores[:, :1] / ((cur - prompt_len) ** length_penalty)
+            best_run = run_scores[:, :1] / (((max_length if es == 2 else cur) - prompt_len) ** length_penalty)     # TF5:gen:3044-3048
             worst_fin = torch.where(finished, beam_scores.min(dim=1, keepdim=True)[0], torch.full_like(beam_scores, -1.0e9))
             unsat = unsat & torch.any(best_run > worst_fin, dim=-1, keepdim=True)
-            if not (bool(unsat.any()) and not bool(hits.all())):
+            if not (bool(unsat.any()) and not (es == 1 and bool(finished.all())) and not bool(hits.all())):     # TF5:gen:3055-3075
                 break
         out = sequences[:, 0, :] if n_ret == 1 else sequences[:, :n_ret, :].reshape(B * n_ret, -1)
         sc = beam_scores[:, 0] if n_ret == 1 else beam_scores[:, :n_ret].reshape(-1)

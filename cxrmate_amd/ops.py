@@ -1150,6 +1150,55 @@ def logits_process_(scores, ids, cur, eos=-1, penalty=1.0, ngram=0, min_length=0
     return scores
 
 
+class ConstraintTables:
+    """Device tables of the token constraints for cxr_logits_constrain_f32 (csrc/logits_proc.hip), built once per generate() call from host lists:
+    sequence_bias = [(ids tuple, float bias), ...] in the caller's order, bad_words = [ids tuple, ...] (single [eos] entries already dropped),
+    forced_bos = id | None, forced_eos = ids, suppress / begin_suppress = ids (duplicates and ids >= V allowed), max_length of forced_eos,
+    begin_index of begin_suppress. Each group of sequence entries is sorted stably by (last id, length > 1): one thread then walks a token's run in
+    the order the library adds the biases (the length-1 entry first, the multi-token entries in the caller's order)."""
+
+    def __init__(self, device, sequence_bias=(), bad_words=(), forced_bos=None, forced_eos=(), suppress=(), begin_suppress=(), max_length=0,
+                 begin_index=-1):
+        order = lambda e: (e[0][-1], len(e[0]) > 1)              # noqa: E731  (sorted() is stable)
+        bias = sorted(((tuple(k), float(b)) for k, b in sequence_bias), key=order)
+        bad = sorted(((tuple(k), float("-inf")) for k in bad_words), key=order)
+        entries = bias + bad
+        assert all(len(k) > 0 for k, _ in entries)
+        self.n_bias, self.n_seq = len(bias), len(entries)
+        off = [0]
+        for k, _ in entries:
+            off.append(off[-1] + len(k))
+        assert off[-1] < 2 ** 31
+
+        def dev(vals, dtype):
+            return torch.tensor(list(vals), dtype=dtype, device=device) if len(vals) else None
+        self.seq_tok = dev([t for k, _ in entries for t in k], torch.int64)
+        self.seq_off = dev(off, torch.int32) if entries else None
+        self.seq_bias = dev([b for _, b in entries], torch.float32)
+        forced_eos = list(forced_eos)
+        self.n_forced_bos, self.n_forced_eos = int(forced_bos is not None), len(forced_eos)
+        self.forced = dev(([int(forced_bos)] if forced_bos is not None else []) + [int(t) for t in forced_eos], torch.int64)
+        self.suppress, self.n_suppress = dev([int(t) for t in suppress], torch.int64), len(suppress)
+        self.begin_suppress, self.n_begin = dev([int(t) for t in begin_suppress], torch.int64), len(begin_suppress)
+        self.max_length, self.begin_index = int(max_length), int(begin_index)
+
+
+def logits_constrain_(scores, ids, cur, eos=-1, penalty=1.0, ngram=0, min_length=0, tables=None):
+    """Token constraints and the three generation controls of logits_process_ in place on fp32 score rows [R, V], one launch (csrc/logits_proc.hip;
+    include/cxrmate_hip.h cxr_logits_constrain_f32), over the history ids[:, :cur] (int64 [R, >= cur], unit column stride). tables: ConstraintTables."""
+    R, V = scores.shape
+    assert scores.dtype == torch.float32 and scores.stride(1) == 1
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == R and ids.stride(1) == 1 and ids.shape[1] >= cur
+    assert isinstance(tables, ConstraintTables)
+    if cur > LOGITS_PROCESS_MAX_HIST:
+        raise ValueError(f"generation controls take histories of at most {LOGITS_PROCESS_MAX_HIST} ids (got {cur})")
+    t = tables
+    LIB.call("cxr_logits_constrain_f32", _p(scores), scores.stride(0), _p(ids), ids.stride(0), R, V, int(cur), int(eos), float(penalty), int(ngram),
+             int(min_length), _p(t.seq_tok), _p(t.seq_off), _p(t.seq_bias), t.n_bias, t.n_seq, _p(t.forced), t.n_forced_bos, t.n_forced_eos,
+             t.max_length, _p(t.suppress), t.n_suppress, _p(t.begin_suppress), t.n_begin, t.begin_index, _s())
+    return scores
+
+
 # ------------------------------------------------------------------------------------------------ optimiser / plumbing
 def adamw_step(p, g, m, v, p16, lr, b1, b2, eps, wd, step, gscale=1.0, step_dev=None):
     """step >= 1: host step count. step == 0 with step_dev (int32 device scalar): the kernel reads the count itself (graph replay)."""
@@ -1250,16 +1299,27 @@ def beam_ws(rows, V, nb, device):
 
 
 def beam_step(logits, running, sequences, run_scores, beam_scores, finished, unsat, allhit, beam_idx, cur, max_length, eos, div, ws=None,
-              logprobs=False, bidx=None):
+              logprobs=False, bidx=None, early=None):
     """One device-side beam-search step (csrc/decode.hip beam_scan_kernel + beam_step_kernel; include/cxrmate_hip.h cxr_beam_step). Beam-major rows.
     logprobs=True: `logits` are log-probs already processed by the generation controls, taken as they are (cxr_beam_step_lp).
-    bidx=(run_bidx, fin_bidx): int32 [nb, B, L] beam-index histories of the running and finished beams, kept in the same launch (cxr_beam_step_idx)."""
+    bidx=(run_bidx, fin_bidx): int32 [nb, B, L] beam-index histories of the running and finished beams, kept in the same launch (cxr_beam_step_idx).
+    early=(mode, div_run, allfin): early_stopping 1 = True / 2 = "never" (0 = False), the divisor of the improvement test and the int32 [2, B]
+    "finished set is full" flags (cxr_beam_step_es; every combination of logprobs and bidx)."""
     nb, B, L = running.shape
     R, V = logits.shape
     assert R == nb * B and logits.dtype == torch.float32 and running.is_contiguous() and sequences.is_contiguous()
     if ws is None:
         ws = beam_ws(R, V, nb, logits.device)
     assert ws.numel() >= R * ((V + 4095) // 4096) * (2 + 4 * nb)
+    if early is not None:                                   # (mode, div_run, allfin): cxr_beam_step_es
+        mode, div_run, allfin = early
+        assert mode in (0, 1, 2) and (mode != 1 or (allfin is not None and allfin.dtype == torch.int32 and allfin.shape == (2, B)))
+        for t in bidx or ():
+            assert t.dtype == torch.int32 and t.shape == (nb, B, L) and t.is_contiguous(), (t.dtype, t.shape)
+        LIB.call("cxr_beam_step_es", _p(logits), logits.stride(0), _p(running), _p(sequences), _p(run_scores), _p(beam_scores), _p(finished),
+                 _p(unsat), _p(allhit), _p(allfin), _p(beam_idx), _p(ws), _p(bidx[0]) if bidx else None, _p(bidx[1]) if bidx else None, B, nb, V, L,
+                 int(cur), int(max_length), int(eos), float(div), float(div_run), int(mode), int(bool(logprobs)), _s())
+        return
     if bidx is not None:
         for t in bidx:
             assert t.dtype == torch.int32 and t.shape == (nb, B, L) and t.is_contiguous(), (t.dtype, t.shape)

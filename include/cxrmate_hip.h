@@ -325,6 +325,21 @@ int cxr_log_softmax_rows(float* x, long ld, long R, int V, const float* add_row,
 int cxr_logits_process_f32(float* logits, long ld, const long* ids, long ids_ld, long R, int V, int cur, long eos, float penalty, int ngram,
                            int min_length, hipStream_t stream);
 
+/* ---- token constraints (TF5 logits_process.py: SequenceBiasLogitsProcessor :1211, NoBadWordsLogitsProcessor :1395, ForcedBOSTokenLogitsProcessor
+ * :1556, ForcedEOSTokenLogitsProcessor :1601, SuppressTokensAtBeginLogitsProcessor :1816, SuppressTokensLogitsProcessor :1869) and the three
+ * controls of cxr_logits_process_f32 (same arguments, same meaning) in ONE launch, in the order of TF5:gen:1123-1293: sequence_bias -> repetition
+ * penalty -> n-gram ban -> bad words -> min length -> forced_bos -> forced_eos -> suppress -> begin_suppress. Sequence table: entry e is the ids
+ * seq_tok[seq_off[e] .. seq_off[e + 1]) (int64 flat, int32 offsets [n_seq + 1], every entry non-empty) with bias seq_bias[e] (fp32); entries
+ * [0, n_bias) are sequence_bias, [n_bias, n_seq) bad words (bias -inf); within each group the caller sorts them stably by (last id, length > 1).
+ * A length-1 entry hits on every step, a length-k entry when k <= cur and the history ends in its first k - 1 ids; the fp32 sum of a token's hitting
+ * biases (in table order, from 0) is added to its score once. forced: n_forced_bos (0 or 1) ids, then n_forced_eos ids; at cur == 1 resp.
+ * cur == max_length - 1 the row becomes -inf and the ids 0. suppress ids -> -inf on every step, begin_suppress ids when cur == begin_index; ids
+ * outside [0, V) are ignored. One workgroup per row; capturable (no host reads, no allocation). */
+int cxr_logits_constrain_f32(float* logits, long ld, const long* ids, long ids_ld, long R, int V, int cur, long eos, float penalty, int ngram,
+                             int min_length, const long* seq_tok, const int* seq_off, const float* seq_bias, int n_bias, int n_seq,
+                             const long* forced, int n_forced_bos, int n_forced_eos, int max_length, const long* suppress, int n_suppress,
+                             const long* begin_suppress, int n_begin, int begin_index, hipStream_t stream);
+
 /* ---- per-step outputs of generate (TF5:gen:2902-2904 _sample, :3393-3396 _beam_search: output_logits / output_scores). One pass over the fp32 score
  * rows x [R, V] (row stride ld) of a decode step: logits_out (optional) <- the rows as they are; scores_out (optional) <- the rows as they are, or
  * their log_softmax when log_softmax != 0 (-inf entries stay -inf). Both outputs are contiguous [R, V], input row r (beam-major, r = beam * S +
@@ -450,6 +465,15 @@ int cxr_beam_step_lp(const float* logprobs, long ld, long* running, long* sequen
 int cxr_beam_step_idx(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
                       int* unsat, int* allhit, long* beam_idx, float* ws, int* run_bidx, int* fin_bidx, int B, int nb, int V, int L, int cur,
                       int max_length, long eos, float div, int logprobs, hipStream_t stream);
+/* Any of the three steps above with early_stopping (TF5:gen _check_early_stop_heuristic :3008, _beam_search_has_unfinished_sequences :3055,
+ * _update_finished_beams :3150-3204). early_stopping 0 = False (the same search), 1 = True: a study whose finished set is full takes no more
+ * hypotheses and the search stops once every study's is full (allfin int32 [2,B], double-buffered by the parity of `cur`, 0 at the start; may be
+ * null in the other modes), 2 = "never": the improvement test divides the best running score by div_run = (max_length - prompt_len) **
+ * length_penalty, which the caller passes when length_penalty > 0 (else div_run = div). run_bidx / fin_bidx may both be null; logprobs as in
+ * cxr_beam_step_idx. */
+int cxr_beam_step_es(const float* logits, long ld, long* running, long* sequences, float* run_scores, float* beam_scores, unsigned char* finished,
+                     int* unsat, int* allhit, int* allfin, long* beam_idx, float* ws, int* run_bidx, int* fin_bidx, int B, int nb, int V, int L,
+                     int cur, int max_length, long eos, float div, float div_run, int early_stopping, int logprobs, hipStream_t stream);
 /* out[i][r, :rows, :] = in[i][idx[r], :rows, :] for n <= 16 tensors [B, *, C] of one geometry (host arrays of device pointers): the KV-cache
  * reorder of a beam step for all layers in one launch (TF5:gen:3468-3478) */
 int cxr_gather_batch_multi_bf16(const void* const* in, void* const* out, int n, long bs, long rs, const long* idx, int B, int rows, int C,
