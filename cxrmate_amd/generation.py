@@ -10,6 +10,10 @@ the sampled sequence is re-scored by ONE teacher-forced pass whose per-step inpu
 """
 from __future__ import annotations
 
+import numbers
+from dataclasses import dataclass, fields
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -143,16 +147,109 @@ def token_constraints(vocab_size, eos_token_id, prompt_len, max_length, sequence
 
 
 def constraint_tables(cons, device):
-    bias, bad, fbos, feos, suppress, begin, max_length, begin_index = cons
-    return ops.ConstraintTables(device, bias, bad, fbos, feos, suppress, begin, max_length, begin_index)
+    return ops.ConstraintTables(device, *cons)               # token_constraints() describes them in the order of the tables' arguments
 
 
-def process_scores_(scores, ids, cur, eos, procs, tables=None):
-    """The processors of one step, one launch: procs = (repetition penalty, n-gram size, absolute min length) -> cxr_logits_process_f32;
-    procs = (..., token constraints) -> cxr_logits_constrain_f32 over the constraints' device tables."""
-    if len(procs) == 3:
-        return ops.logits_process_(scores, ids, cur, eos, *procs)
-    return ops.logits_constrain_(scores, ids, cur, eos, *procs[:3], tables=tables)
+class Controls(NamedTuple):
+    """The generation controls of one call: repetition penalty (1.0: none), n-gram size (0: none), absolute minimum length (0: none) and the token
+    constraints (what token_constraints() returns, or None)."""
+    penalty: float = 1.0
+    ngram: int = 0
+    min_abs: int = 0
+    cons: tuple | None = None
+
+    @property
+    def active(self):                                        # does a step launch the processors at all?
+        return self.penalty != 1.0 or self.ngram > 0 or self.min_abs > 0 or self.cons is not None
+
+    @property
+    def constrained(self):                                   # ... and is it the constraint kernel, over the constraints' device tables?
+        return self.cons is not None
+
+
+RECORDED = ("scores", "logits")                                # the per-step outputs, in the order TF5's generate outputs list them
+
+
+class Record(NamedTuple):
+    """The per-step outputs a call asks for (output_logits / output_scores): which of the two, and the number of row groups of the study-major
+    permutation they are stored under (decode row g * (rows // row_groups) + study -> output row study * row_groups + g)."""
+    logits: bool = False
+    scores: bool = False
+    row_groups: int = 1
+
+    @property
+    def on(self):
+        return self.logits or self.scores
+
+
+def _plain(v):
+    return v is None or isinstance(v, (str, numbers.Number)) or (isinstance(v, tuple) and all(_plain(e) for e in v))
+
+
+@dataclass(frozen=True)
+class StepPlan:
+    """Everything the decode steps of one generate() call depend on besides their column: built once per call, handed to every DecodeSession.step,
+    and -- being compared and hashed by VALUE -- the options' part of the key a captured step graph is stored under. Equal options give equal
+    plans (the graphs are replayed), any different option an unequal one (never a graph captured for other options). Every field holds None,
+    numbers, strings or tuples of them: a list, tensor, dict or function (unhashable, or compared by identity) is refused at construction."""
+    kind: str                                  # "greedy" | "sample" | "pair" (first half of the rows sampled, second half argmax) | "beam"
+    special: tuple                             # separator ids of the token types; "pair": (ids of the sampled half, ids of the greedy half)
+    mask_token_id: int | None
+    bos: int
+    eos: int | None
+    pad: int | None
+    max_length: int
+    train: bool                                # dropout on (model.training)
+    controls: Controls = Controls()
+    record: Record = Record()
+    top_k: int = 0                             # "sample" / "pair": the warpers of the sampled rows
+    temperature: float = 1.0
+    top_p: float = 1.0
+    num_beams: int = 1                         # "beam" (the other kinds leave these four alone: their graphs serve every prompt length)
+    length_penalty: float = 1.0
+    prompt_len: int = 0                        # columns before the first generated one, the prepended BOS included
+    early_stopping: int = 0                    # early_stopping_mode(): 0 False, 1 True, 2 "never"
+
+    def __post_init__(self):
+        bad = [f.name for f in fields(self) if not _plain(getattr(self, f.name))]
+        if bad:
+            raise TypeError(f"StepPlan fields {bad}: a plan holds None, numbers, strings and tuples of them only")
+
+
+def process_scores_(scores, ids, cur, eos, controls, tables=None):
+    """The processors of one step, one launch: the three controls alone -> cxr_logits_process_f32; with token constraints ->
+    cxr_logits_constrain_f32 over the constraints' device tables."""
+    if controls.constrained:
+        return ops.logits_constrain_(scores, ids, cur, eos, controls.penalty, controls.ngram, controls.min_abs, tables=tables)
+    return ops.logits_process_(scores, ids, cur, eos, controls.penalty, controls.ngram, controls.min_abs)
+
+
+def score_step_(logits, ids, cur, plan, lo, so, tables=None):
+    """The per-step outputs and the processors of one step in TF5's order, in place on the fp32 rows `logits`: raw logits -> lo, [beam: log_softmax,]
+    the processors over the history ids[:, :cur], processed scores -> so (lo / so: output slots or None; csrc/gen_record.hip stores them
+    study-major). Without processors one launch records both (or nothing is launched) and a beam search takes its log_softmax in the launch
+    that follows (ops.beam_step / log_softmax_rows_(add_row=)); with them the beam path processes log-probs (TF5 utils.py:3388-3389)."""
+    beam, nb = plan.kind == "beam", plan.record.row_groups
+    if not plan.controls.active:
+        if lo is not None or so is not None:
+            ops.gen_record(logits, lo, so, log_softmax=beam, nb=nb)
+        return
+    if lo is not None:
+        ops.gen_record(logits, lo, nb=nb)
+    if beam:
+        ops.log_softmax_rows_(logits)
+    process_scores_(logits, ids, cur, -1 if plan.eos is None else plan.eos, plan.controls, tables)
+    if so is not None:
+        ops.gen_record(logits, None, so, nb=nb)
+
+
+def trim_at_eos(sequences, prompt_len, eos):
+    """HF stops at the step on which the last row finishes: -> sequences up to the first EOS of the longest row (one host read)."""
+    if eos is None:
+        return sequences
+    is_eos = sequences[:, prompt_len:] == eos
+    lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((sequences.shape[0],), is_eos.shape[1], device=sequences.device))
+    return sequences[:, : prompt_len + int(lens.max())]
 
 
 def early_stopping_mode(early_stopping, length_penalty):
@@ -203,7 +300,8 @@ class DecodeSession:
         # uniforms of every sampling step of a decode, drawn by ONE torch call in reset(): a torch.rand inside a captured step costs three extra
         # tiny launches per replay (the generator's seed / offset refresh in front of the graph + the fill kernel itself)
         self.u_all = torch.zeros((Lmax, rows), dtype=torch.float32, device=dev)
-        self.poll_host = torch.zeros(1, dtype=torch.int32).pin_memory()          # landing pad of the asynchronous EOS poll
+        self.poll_host = torch.zeros(1, dtype=torch.int32).pin_memory()          # landing pad of the asynchronous stop poll (keep_going)
+        self.polled = None                                 # event behind the copy of the last submitted flag
         # per-step inputs of the cached steps (one fused kernel writes them): last token, token type, position, attention mask, and the
         # token-type / position history the teacher-forced re-scoring of the sampled rows needs
         self.new_id = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
@@ -223,7 +321,7 @@ class DecodeSession:
 
     def constraint_tables(self, cons):
         """Device tables of the token constraints `cons`, owned by the session: step graphs bake their addresses, so a table lives as long as the
-        graphs keyed by it (the `mode` key of a step carries `cons`). Built outside any capture; a ninth description drops the tables AND the graphs."""
+        graphs keyed by it (the plan in a step's key carries `cons`). Built outside any capture; a ninth description drops the tables AND the graphs."""
         if cons not in self.cons:
             if len(self.cons) >= 8:
                 self.cons.clear()
@@ -261,15 +359,19 @@ class DecodeSession:
             st["allfin"].zero_()
         return st
 
-    def record_buffers(self, logits, scores):
-        """Static slots of the per-step outputs a call asks for: [Lmax, rows, V] fp32, step column c -> slot c (a step graph bakes its slot's
-        address). Allocated on the first call that asks for them and never replaced, so graphs captured over them stay valid; calls without the
-        flags neither allocate nor touch them."""
+    def record_buffers(self, record):
+        """Static slots of the per-step outputs a call asks for, by name: [Lmax, rows, V] fp32, step column c -> slot c (a step graph bakes its
+        slot's address). Allocated on the first call that asks for them and never replaced, so graphs captured over them stay valid; calls
+        without the flags neither allocate nor touch them."""
         V = self.model.config.decoder.vocab_size
-        for name, want in (("logits", logits), ("scores", scores)):
-            if want and name not in self.rec_bufs:
+        for name in RECORDED:
+            if getattr(record, name) and name not in self.rec_bufs:
                 self.rec_bufs[name] = torch.empty((self.Lmax, self.ids.shape[0], V), dtype=torch.float32, device=self.ids.device)
-        return self.rec_bufs.get("logits") if logits else None, self.rec_bufs.get("scores") if scores else None
+        return {name: self.rec_bufs[name] for name in RECORDED if getattr(record, name)}
+
+    def records(self, record, first, steps):
+        """One copy of the recorded outputs of steps first .. first+steps-1 (the session is reused by the next call): name -> tuple of [rows, V]."""
+        return {name: buf[first:first + steps].clone().unbind(0) for name, buf in self.record_buffers(record).items()}
 
     def _swap_caches(self, n=1):
         c = self.cache
@@ -277,7 +379,7 @@ class DecodeSession:
             c.k, c.k2 = c.k2, c.k
             c.v, c.v2 = c.v2, c.v
 
-    def reset(self, ids0, enc16, enc_mask8):
+    def reset(self, ids0, enc16, enc_mask8, plan):
         m = self.model
         m._dec.prepare()                           # weight-derived buffers (LoRA merge) are refreshed IN PLACE: captured pointers stay valid
         m._dec.refresh_decode_packs()              # ... as are the packed / LayerNorm-folded decode weights the replayed steps stream
@@ -299,21 +401,40 @@ class DecodeSession:
         if m.training:
             self.seed.copy_(m.next_dropout_seed())
         self.u_all.uniform_()                      # torch's CUDA generator: reproducible under torch.manual_seed
+        self.polled = None
+        # what the steps of `plan` bake the address of, made before the first of them is captured (never from inside a capture)
+        self.record_buffers(plan.record)
+        if plan.controls.constrained:
+            self.constraint_tables(plan.controls.cons)
 
-    def step(self, cur, strip, mode, n=1):
-        """Append tokens cur .. cur+n-1 (0-based columns of self.ids). mode = (kind, special_token_ids, mask_token_id, top_k, temperature, eos, pad,
-        train, top_p, procs, rec); procs = (repetition penalty, n-gram size, absolute min length[, token constraints]) of the generation controls,
-        or None (the constraints' tables: constraint_tables, built before the first step); rec =
-        (record logits, record scores, row groups nb of the study-major permutation) of output_logits / output_scores, or None. The n cached
-        steps are ONE hipGraph (a replay costs ~9 us of launch overhead whatever it holds: per token at n = 1, per 8 tokens at n = 8)."""
+    def keep_going(self, flag):
+        """The stop poll of a decode loop, one poll behind: False when the flag the PREVIOUS call submitted has landed as 0; else flag() (int32 [1]
+        on the device, 0 = every row is done) is copied to the pinned word and -> True. The copy is only waited for at the next poll, so the host
+        keeps enqueueing steps while the GPU works (a blocking .item() drained the queue 32 times per decode); the caller trims the overshoot."""
+        if self.polled is not None:
+            self.polled.synchronize()
+            if int(self.poll_host[0]) == 0:
+                return False
+        self.poll_host.copy_(flag(), non_blocking=True)
+        self.polled = torch.cuda.Event()
+        self.polled.record()
+        return True
+
+    def step(self, cur, strip, plan, n=1):
+        """Append tokens cur .. cur+n-1 (0-based columns of self.ids; strip: leading columns the decoder is not fed) as the StepPlan `plan`
+        describes: plan.kind selects sampling / argmax / beam bookkeeping, plan.controls the processors (the constraints' tables:
+        constraint_tables, built before the first step), plan.record the per-step outputs (their slots: record_buffers, likewise). The n cached
+        steps are ONE hipGraph, stored under (cur, n, strip, plan) (a replay costs ~9 us of launch overhead whatever it holds: per token at
+        n = 1, per 8 tokens at n = 8)."""
         prefill = self.cache.len == 0
         if prefill or not self.model.graph_decode:
             for c in range(cur, cur + n):
-                self._run(c, strip, mode, prefill and c == cur)
+                self._run(c, strip, plan, prefill and c == cur)
             return
-        key = (cur, n, strip, mode)
+        key = (cur, n, strip, plan)
         hit = self.graphs.get(key)
-        if hit is None:
+        captured = hit is None
+        if captured:
             g = torch.cuda.CUDAGraph()
             if self.pool is None:
                 self.pool = torch.cuda.graph_pool_handle()
@@ -321,36 +442,36 @@ class DecodeSession:
             torch.cuda.synchronize()
             with ops.graph_capture(g, pool=self.pool):
                 for c in range(cur, cur + n):
-                    self._run(c, strip, mode, False)
+                    self._run(c, strip, plan, False)
             self.cache.len = keep                      # capture does not execute: replay below performs the steps
             hit = (g, self.last_tt, self.last_pos)     # the last step's token-type / position outputs live in the session's history buffers
             self.graphs[key] = hit
-            captured = True
-        else:
-            captured = False
         g, self.last_tt, self.last_pos = hit
         g.replay()
-        if mode[0] == "beam" and not captured:         # the capture pass already walked the ping-pong of the reordered caches
+        if plan.kind == "beam" and not captured:       # the capture pass already walked the ping-pong of the reordered caches
             self._swap_caches(n)
         self.cache.len = cur + n - 1 - strip
 
-    def _run(self, cur, strip, mode, prefill):
-        m = self.model
-        kind, special, mask_token_id, top_k, temperature, eos, pad, train, top_p, procs, rec = mode
+    def _run(self, cur, strip, plan, prefill):
+        """The launches of one step: decoder -> logits of column `cur`, score_step_ (records, processors), then by plan.kind one selection launch
+        (top_k / temperature / top_p on the sampled rows; finished rows emit plan.pad once plan.eos was drawn) or the beam step (num_beams,
+        length_penalty, prompt_len, max_length, early_stopping) and the cache reorder. prefill: the whole prompt is fed, by torch ops."""
+        m, train, special = self.model, plan.train, plan.special
+        eos = -1 if plan.eos is None else plan.eos
         # per-step outputs (csrc/gen_record.hip): raw logits before any processor, scores as TF5 stores them; slot `cur` of the session's buffers
-        lo, so = self.record_buffers(rec[0], rec[1]) if rec is not None else (None, None)
-        lo, so = None if lo is None else lo[cur], None if so is None else so[cur]
-        tables = self.cons[procs[3]] if procs is not None and len(procs) > 3 else None
+        slots = self.record_buffers(plan.record)
+        lo, so = (slots[name][cur] if name in slots else None for name in ("logits", "scores"))
+        tables = self.cons[plan.controls.cons] if plan.controls.constrained else None
         if prefill:
             fed = self.ids[:, strip:cur]
-            new, mask, tt, pos = m._step_inputs(fed, special, mask_token_id, prefill=True)
+            new, mask, tt, pos = m._step_inputs(fed, special, plan.mask_token_id, prefill=True)
             new, tt, pos = new.contiguous(), tt.contiguous(), None if pos is None else pos.contiguous()
         else:                                                      # one launch: last token, token type, position, mask (+ their history)
-            pair = isinstance(special, tuple) and special and isinstance(special[0], (tuple, list))
-            sp0, sp1 = (special[0], special[1]) if pair else (special, special)
+            pair = plan.kind == "pair"
+            sp0, sp1 = special if pair else (special, special)
             longi = m.kind == "longitudinal"
             step_args = (self.ids, strip, cur, list(sp0), list(sp1), [0, 1, 0, 1] if longi else None, self.B // 2 if pair else self.B,
-                         mask_token_id if longi else -1, self.new_id, self.tt1, self.pos1 if longi else None,
+                         plan.mask_token_id if longi else -1, self.new_id, self.tt1, self.pos1 if longi else None,
                          self.mask8 if longi else None, self.tt_hist, self.pos_hist if longi else None)
             mask = self.mask8[:, :cur - strip] if longi else None
             if (m._dec.fused_step_ok(self.cache, self.B, self.enc16) and len(sp0) <= 4 and len(sp1) <= 4
@@ -366,46 +487,27 @@ class DecodeSession:
                 pos = self.pos1 if longi else None
         if new is not None:
             logits = m._dec.decode(self.cache, new, self.enc16, self.enc_mask8, mask, tt, pos, train=train, seed=self.seed)
-        if kind == "beam":                                          # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
-            nb, penalty, (prompt_len, max_length, es) = top_k, temperature, top_p
-            st, c = self.beam, self.cache
-            if procs is None and (lo is not None or so is not None):  # scores = log_softmax(logits) (TF5:gen:3387, :3396), study-major rows
-                ops.gen_record(logits, lo, so, log_softmax=True, nb=nb)
-            if procs is not None:                                   # TF5 processes log_softmax(logits) on the beam path (utils.py:3388-3389)
-                if lo is not None:
-                    ops.gen_record(logits, lo, nb=nb)
-                ops.log_softmax_rows_(logits)
-                process_scores_(logits, self.ids, cur, -1 if eos is None else eos, procs, tables)
-                if so is not None:
-                    ops.gen_record(logits, None, so, nb=nb)
+        score_step_(logits, self.ids, cur, plan, lo, so, tables)
+        if plan.kind == "beam":                                     # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
+            nb, es, st, c = plan.num_beams, plan.early_stopping, self.beam, self.cache
             ops.beam_step(logits, self.ids.view(nb, self.B // nb, self.Lmax), st["sequences"], st["run_scores"], st["beam_scores"], st["finished"],
-                          st["unsat"], st["allhit"], st["beam_idx"], cur, max_length, -1 if eos is None else eos,
-                          float(cur + 1 - prompt_len) ** penalty, ws=st["ws"], logprobs=procs is not None,
-                          bidx=(st["run_bidx"], st["fin_bidx"]) if rec is not None else None,
-                          early=None if not es else (es, float(max_length - prompt_len) ** penalty if es == 2 else 0.0, st.get("allfin")))
+                          st["unsat"], st["allhit"], st["beam_idx"], cur, plan.max_length, eos,
+                          float(cur + 1 - plan.prompt_len) ** plan.length_penalty, ws=st["ws"], logprobs=plan.controls.active,
+                          bidx=(st["run_bidx"], st["fin_bidx"]) if plan.record.on else None,
+                          early=None if not es else (es, float(plan.max_length - plan.prompt_len) ** plan.length_penalty if es == 2 else 0.0,
+                                                     st.get("allfin")))
             ops.gather_batch_multi(c.k + c.v, st["beam_idx"], c.len, c.k2 + c.v2)
             self._swap_caches()
             self.last_tt = self.last_pos = None
             return
-        unf = self.unfinished if eos is not None else None
-        eos_ = eos if eos is not None else -1
-        n_smp = {"greedy": 0, "sample": self.B, "pair": self.B // 2}[kind]      # rows [0, n_smp) sample, the rest take the argmax
+        unf = self.unfinished if plan.eos is not None else None
+        n_smp = {"greedy": 0, "sample": self.B, "pair": self.B // 2}[plan.kind]      # rows [0, n_smp) sample, the rest take the argmax
         col = self.ids[:, cur]                                                  # the selection kernels write straight into the id buffer
-        nperm = rec[2] if rec is not None else 1
-        if procs is None and (lo is not None or so is not None):
-            ops.gen_record(logits, lo, so, nb=nperm)
-        if procs is not None:                                                   # processors before the warpers of select_token (TF5 order)
-            if lo is not None:
-                ops.gen_record(logits, lo, nb=nperm)
-            process_scores_(logits, self.ids, cur, eos_, procs, tables)
-            if so is not None:
-                ops.gen_record(logits, None, so, nb=nperm)
         if n_smp:                                                               # one launch for sampled + greedy rows
-            u = self.u_all[cur, :n_smp]
-            ops.select_token(logits, mode=1, temperature=temperature, top_k=top_k or 0, u=u, unfinished=unf, eos=eos_, pad=pad or 0, out=col,
-                             top_p=top_p, n_sample=n_smp)
+            ops.select_token(logits, mode=1, temperature=plan.temperature, top_k=plan.top_k, u=self.u_all[cur, :n_smp], unfinished=unf, eos=eos,
+                             pad=plan.pad or 0, out=col, top_p=plan.top_p, n_sample=n_smp)
         else:
-            ops.select_token(logits, unfinished=unf, eos=eos_, pad=pad or 0, out=col)
+            ops.select_token(logits, unfinished=unf, eos=eos, pad=plan.pad or 0, out=col)
         if prefill:
             self.last_tt, self.last_pos = tt, pos
         else:                                                      # views of the history columns this step wrote (stable across graph replays)
@@ -462,46 +564,35 @@ class GenerationMixin:
         forced_bos_token_id, forced_eos_token_id) follow transformers 5.15.0's processors, in its order, in one launch per step
         (csrc/logits_proc.hip); early_stopping is False, True or "never" (beam search)."""
         from .modelling import ModelOutput
-        passed = dict(max_length=max_length, max_new_tokens=max_new_tokens, bos_token_id=bos_token_id, eos_token_id=eos_token_id,
-                      pad_token_id=pad_token_id, num_beams=num_beams, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                      output_scores=output_scores, return_dict_in_generate=return_dict_in_generate, use_cache=use_cache,
-                      length_penalty=length_penalty, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                      min_length=min_length, min_new_tokens=min_new_tokens, num_return_sequences=num_return_sequences, output_logits=output_logits,
-                      bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                      sequence_bias=sequence_bias, forced_bos_token_id=forced_bos_token_id, forced_eos_token_id=forced_eos_token_id,
-                      early_stopping=early_stopping)
-        o = resolve_generation_options(passed, generation_config)
-        (max_length, max_new_tokens, bos_token_id, eos_token_id, pad_token_id, num_beams, do_sample, top_k, top_p, temperature, output_scores,
-         return_dict_in_generate, use_cache, length_penalty, repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens,
-         num_return_sequences, output_logits) = (o[k] for k in list(GENERATION_DEFAULTS)[:20])
-        es = early_stopping_mode(o["early_stopping"], 1.0 if length_penalty is None else length_penalty)
+        args = locals()
+        o = resolve_generation_options({k: args[k] for k in GENERATION_DEFAULTS}, generation_config)
+        bos_token_id, eos_token_id, pad_token_id = o["bos_token_id"], o["eos_token_id"], o["pad_token_id"]
+        do_sample, output_scores, return_dict_in_generate = o["do_sample"], o["output_scores"], o["return_dict_in_generate"]
+        es = early_stopping_mode(o["early_stopping"], 1.0 if o["length_penalty"] is None else o["length_penalty"])
         if inputs is not None and pixel_values is None:
             pixel_values = inputs
         if special_token_ids is None:
             raise ValueError("special_token_ids is required (reference prepare_inputs_for_generation signature)")
         if self.kind == "longitudinal" and mask_token_id is None:
             raise ValueError("mask_token_id is required for the longitudinal model")
-        top_p = 1.0 if top_p is None else float(top_p)
-        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
-        num_beams = 1 if num_beams is None else int(num_beams)
+        top_k, temperature, top_p = o["top_k"], o["temperature"], 1.0 if o["top_p"] is None else float(o["top_p"])
+        n_ret = 1 if o["num_return_sequences"] is None else int(o["num_return_sequences"])
+        num_beams = 1 if o["num_beams"] is None else int(o["num_beams"])
         if n_ret > 1 and num_beams == 1 and not do_sample:            # TF5 configuration_utils.py:788-805
             raise ValueError(f"Greedy methods (do_sample != True) without beam search do not support `num_return_sequences` different than 1 "
                              f"(got {n_ret}).")
         if num_beams > 1 and n_ret > num_beams:
             raise ValueError(f"`num_return_sequences` ({n_ret}) has to be smaller or equal to `num_beams` ({num_beams}).")
-        penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        penalty = 1.0 if o["repetition_penalty"] is None else float(o["repetition_penalty"])
         if not penalty > 0.0:
-            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
-        ngram = int(no_repeat_ngram_size or 0)
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {o['repetition_penalty']}")
+        ngram = int(o["no_repeat_ngram_size"] or 0)
         if ngram <= 0 or ngram > ops.LOGITS_PROCESS_MAX_HIST:       # TF5 adds the processor for sizes > 0 only; a size above the longest history
             ngram = 0                                                # can never complete an n-gram
         with torch.no_grad():
             if encoder_outputs is None:
                 encoder_outputs = self._encode(pixel_values)
-        enc = encoder_outputs[0]
-        enc_mask = encoder_outputs.get("attention_mask") if isinstance(encoder_outputs, dict) else None
-        if self.kind == "single":
-            enc_mask = None
+        enc, enc_mask = self._encoder_rows(encoder_outputs)
         dev = self.device
         B = enc.shape[0]
         prompt = decoder_input_ids if decoder_input_ids is not None else input_ids
@@ -511,63 +602,56 @@ class GenerationMixin:
         else:
             prompt = prompt.to(device=dev, dtype=torch.int64)
             ids = torch.cat([start, prompt], dim=-1) if bool((prompt[:, 0] != bos_token_id).all()) else prompt
-        if max_new_tokens is not None:
-            max_length = ids.shape[1] + max_new_tokens
+        prompt_len = ids.shape[1]
+        max_length = o["max_length"]
+        if o["max_new_tokens"] is not None:
+            max_length = prompt_len + o["max_new_tokens"]
         if max_length is None:
-            max_length = 20 + ids.shape[1]
+            max_length = 20 + prompt_len
         # generation controls (TF5 logits processors): min_new_tokens takes precedence over min_length as an absolute length (TF5:gen:1760);
         # EOS bans only while the history is shorter than it, so a minimum the prompt already reaches launches nothing
-        min_abs = (ids.shape[1] + int(min_new_tokens)) if min_new_tokens is not None else int(min_length or 0)
-        min_abs = min_abs if (eos_token_id is not None and min_abs > ids.shape[1]) else 0
-        procs = (penalty, ngram, min_abs) if (penalty != 1.0 or ngram > 0 or min_abs) else None
+        min_abs = (prompt_len + int(o["min_new_tokens"])) if o["min_new_tokens"] is not None else int(o["min_length"] or 0)
+        min_abs = min_abs if (eos_token_id is not None and min_abs > prompt_len) else 0
         # token constraints (TF5 logits processors, validated as the library validates them): with any of them set, ONE launch of the constraint
         # kernel applies them and the three controls above; with none, the launch (or no launch) of before
-        cons = token_constraints(self.config.decoder.vocab_size, eos_token_id, ids.shape[1], max_length, o["sequence_bias"], o["bad_words_ids"],
+        cons = token_constraints(self.config.decoder.vocab_size, eos_token_id, prompt_len, max_length, o["sequence_bias"], o["bad_words_ids"],
                                  o["suppress_tokens"], o["begin_suppress_tokens"], o["forced_bos_token_id"], o["forced_eos_token_id"])
-        if cons is not None:
-            procs = (penalty, ngram, min_abs, cons)
-        if procs is not None and max_length - 1 > ops.LOGITS_PROCESS_MAX_HIST:      # refused before decoding, not at the step that gets there
+        controls = Controls(penalty, ngram, min_abs, cons)
+        if controls.active and max_length - 1 > ops.LOGITS_PROCESS_MAX_HIST:      # refused before decoding, not at the step that gets there
             raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens and the token constraints take histories of "
                              f"at most {ops.LOGITS_PROCESS_MAX_HIST} ids: max_length {max_length} is too long")
-        if procs is not None and do_sample and output_scores:
+        if controls.active and do_sample and output_scores:
             raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_length / min_new_tokens / token constraints together with "
                                       "do_sample=True and output_scores=True are not supported: the differentiable scores are not processed")
-        enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
-        enc_mask8 = None if enc_mask is None else enc_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        enc16, enc_mask8 = self._decoder_feed(enc, enc_mask)
         # per-step outputs (TF5 GenerateOutput fields): recorded only when the dict output asks for them
-        want_logits = bool(output_logits) and bool(return_dict_in_generate)
+        want_logits = bool(o["output_logits"]) and bool(return_dict_in_generate)
         want_scores = bool(output_scores) and bool(return_dict_in_generate)
+        common = dict(special=tuple(special_token_ids), mask_token_id=mask_token_id, bos=bos_token_id, eos=eos_token_id, max_length=int(max_length),
+                      train=bool(self.training), controls=controls)
+        rec_out = {}
         if num_beams > 1:
             if do_sample:
                 raise NotImplementedError("beam sampling is not used by the reference")
+            # device-side search: beam counts with a shared-K/V attention kernel, and a cache the one-launch reorder can address (16 tensors = 8 layers)
+            on_device = self.device_beam_search and num_beams in (2, 4) and 2 * self.config.decoder.num_hidden_layers <= 16
+            # (the device search decodes beam-major rows, stored study-major over num_beams row groups; the host loop's rows are study-major already)
+            plan = StepPlan(kind="beam", **common, pad=0 if pad_token_id is None else pad_token_id,
+                            record=Record(want_logits, want_scores, num_beams if on_device else 1), num_beams=num_beams,
+                            length_penalty=float(o["length_penalty"]), prompt_len=prompt_len, early_stopping=es)
             with torch.no_grad():
-                # device-side search: beam counts with a shared-K/V attention kernel, and a cache the one-launch reorder can address (16 tensors = 8 layers)
-                on_device = self.device_beam_search and num_beams in (2, 4) and 2 * self.config.decoder.num_hidden_layers <= 16
-                search = self._beam_search_session if on_device else self._beam_search
-                record = (want_logits, want_scores) if (want_logits or want_scores) else None
-                rec_out = {}
-                seqs, seq_scores = search(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams,
-                                          bos_token_id, eos_token_id, pad_token_id, length_penalty, procs=procs, n_ret=n_ret,
-                                          record=record, rec_out=rec_out, **({"es": es} if es else {}))
-            if return_dict_in_generate:
-                out = ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None)
-                if want_scores:                                     # TF5 GenerateBeamEncoderDecoderOutput field order
-                    out["scores"] = rec_out["scores"]
-                if want_logits:
-                    out["logits"] = rec_out["logits"]
-                if record is not None:
-                    out["beam_indices"] = rec_out["beam_indices"]
-                return out
+                seqs, seq_scores = (self._beam_search_session if on_device else self._beam_search)(ids, enc16, enc_mask8, plan, n_ret, rec_out)
+            if return_dict_in_generate:         # TF5 GenerateBeamEncoderDecoderOutput field order: rec_out holds scores, logits, beam_indices
+                return ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None, **rec_out)
             return seqs
 
-        prompt_len = ids.shape[1]
-        rec = {"tt": [], "pos": []}
+        rec, keep_inputs = {"tt": [], "pos": []}, (output_scores and do_sample) or record_inputs
         margins = []
         # greedy scores and every call's logits are recorded per step: never served by / decoded along the SCST speculative greedy pass
-        rec_logits, rec_scores = want_logits, want_scores and not do_sample
-        record = (rec_logits, rec_scores, n_ret) if (rec_logits or rec_scores) else None
-        rec_out = {}
-        plain = forced_tokens is None and not return_margins and not record_inputs and procs is None and n_ret == 1 and record is None
+        record = Record(want_logits, want_scores and not do_sample, n_ret)
+        warpers = dict(top_k=int(top_k or 0), temperature=float(temperature), top_p=top_p) if do_sample else {}
+        plan = StepPlan(kind="sample" if do_sample else "greedy", **common, pad=pad_token_id, record=record, **warpers)
+        plain = forced_tokens is None and not return_margins and not record_inputs and not controls.active and n_ret == 1 and not record.on
         if n_ret > 1:
             # sampling of n sequences per study: B * n rows, sample-major (row j * B + b) over ONE copy of the encoder rows when the decode
             # kernels can share them (2 or 4 query rows per K/V stream), else over repeated rows; returned study-major (TF5 repeat_interleave)
@@ -601,14 +685,9 @@ class GenerationMixin:
                                                         bos_token_id, eos_token_id, pad_token_id, top_k=top_k, temperature=temperature, top_p=top_p)
             self._spec_result = (spec_objs, pattern, base, spec_ver)
         elif forced_tokens is None and not return_margins:
-            ids = self._generate_session(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
-                                         pad_token_id, do_sample, top_k, temperature, rec if ((output_scores and do_sample) or record_inputs) else None,
-                                         top_p=top_p, procs=procs, record=record, rec_out=rec_out)
+            ids = self._generate_session(ids, enc16, enc_mask8, plan, rec if keep_inputs else None, rec_out)
         else:
-            ids, margins = self._generate_eager(ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id,
-                                                pad_token_id, forced_tokens, return_margins,
-                                                rec if ((output_scores and do_sample) or record_inputs) else None, procs=procs, record=record,
-                                                rec_out=rec_out)
+            ids, margins = self._generate_eager(ids, enc16, enc_mask8, plan, forced_tokens, rec if keep_inputs else None, rec_out)
         order = None
         if n_ret > 1:
             # the decode's rows are sample-major (row j * B + b); the re-scoring pass runs over the SAME rows in the same order -- dropout masks are
@@ -628,7 +707,7 @@ class GenerationMixin:
             rec = {k: ([None if t is None else t[order] for t in v] if k in ("tt", "pos") else v) for k, v in rec.items()}
         if return_dict_in_generate:
             out = ModelOutput(sequences=ids, scores=scores)
-            if rec_logits:
+            if want_logits:
                 out["logits"] = rec_out["logits"]
             if record_inputs:
                 out["recorded_inputs"] = rec
@@ -638,109 +717,86 @@ class GenerationMixin:
             return out
         return ids
 
-    def _generate_eager(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                        forced_tokens, return_margins, rec=None, procs=None, record=None, rec_out=None):
+    def _generate_eager(self, ids, enc16, enc_mask8, plan, forced_tokens, rec=None, rec_out=None):
         """Eagerly launched greedy loop with per-step argmax / margin capture and optional teacher forcing (parity tests). rec: the per-step
         token-type / position inputs are recorded as _generate_session records them (a sampling call with forced_tokens then returns the processed
-        scores of the FORCED ids: the reference's sampled sequence can be pushed through the grad-enabled generate body). record / rec_out: the
-        per-step logits / processed scores, as _generate_session records them."""
+        scores of the FORCED ids: the reference's sampled sequence can be pushed through the grad-enabled generate body). plan.record / rec_out:
+        the per-step logits / processed scores, as _generate_session records them."""
         dev = self.device
         B = ids.shape[0]
-        prompt_len = ids.shape[1]
+        eos, pad, max_length = plan.eos, plan.pad, plan.max_length
         margins = []
-        got = {"logits": [], "scores": []}
-        tables = constraint_tables(procs[3], dev) if procs is not None and len(procs) > 3 else None
+        got = {name: [] for name in RECORDED if getattr(plan.record, name)}
+        tables = constraint_tables(plan.controls.cons, dev) if plan.controls.constrained else None
         with torch.no_grad():
             cache = self._dec.new_cache(B, max_length, dev)
             unfinished = torch.ones(B, dtype=torch.int32, device=dev)
             step = 0
             seed = self.next_dropout_seed() if self.training else None
             while ids.shape[1] < max_length:
-                fed = self._fed(ids, bos_token_id)
-                new, mask, tt, pos = self._step_inputs(fed, special_token_ids, mask_token_id, prefill=cache.len == 0)
+                fed = self._fed(ids, plan.bos)
+                new, mask, tt, pos = self._step_inputs(fed, plan.special, plan.mask_token_id, prefill=cache.len == 0)
                 if rec is not None:
                     rec["tt"].append(tt.clone())
                     rec["pos"].append(None if pos is None else pos.clone())
                     rec["seed"] = seed
                 logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                           seed=seed)
-                if record is not None and record[0]:
-                    got["logits"].append(ops.gen_record(logits, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[0])
-                if procs is not None:                        # generation controls on the whole running history (BOS, prompt, generated)
-                    process_scores_(logits, ids, ids.shape[1], -1 if eos_token_id is None else eos_token_id, procs, tables)
-                if record is not None and record[1]:
-                    got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device), nb=record[2])[1])
+                self._score_step_kept(logits, ids, ids.shape[1], plan, tables, got)      # the whole running history (BOS, prompt, generated)
                 if forced_tokens is not None:
                     greedy_tok, mg = ops.select_token(logits, need_margin=True)
                     margins.append((greedy_tok, mg))
                     nxt = forced_tokens[:, step].to(dev).clone()
-                    if eos_token_id is not None:
-                        nxt = torch.where(unfinished.bool(), nxt, torch.full_like(nxt, pad_token_id))
-                        unfinished = unfinished & (nxt != eos_token_id).int()
+                    if eos is not None:
+                        nxt = torch.where(unfinished.bool(), nxt, torch.full_like(nxt, pad))
+                        unfinished = unfinished & (nxt != eos).int()
                 else:
-                    nxt, mg = ops.select_token(logits, unfinished=unfinished if eos_token_id is not None else None,
-                                               eos=eos_token_id if eos_token_id is not None else -1, pad=pad_token_id or 0, need_margin=True)
+                    nxt, mg = ops.select_token(logits, unfinished=unfinished if eos is not None else None, eos=eos if eos is not None else -1,
+                                               pad=pad or 0, need_margin=True)
                     margins.append((nxt.clone(), mg))
                 ids = torch.cat([ids, nxt[:, None]], dim=-1)
                 step += 1
                 if forced_tokens is not None and step >= forced_tokens.shape[1]:
                     break
-                if eos_token_id is not None and forced_tokens is None and int(unfinished.max()) == 0:
+                if eos is not None and forced_tokens is None and int(unfinished.max()) == 0:
                     break
-        if rec_out is not None and record is not None:
-            for k, want in zip(("logits", "scores"), record[:2]):
-                if want:
-                    rec_out[k] = tuple(got[k])
+        rec_out.update({name: tuple(kept) for name, kept in got.items()})
         return ids, margins
 
-    def _generate_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, bos_token_id, eos_token_id, pad_token_id,
-                          do_sample, top_k, temperature, rec, top_p=1.0, procs=None, record=None, rec_out=None):
-        """Greedy / top-k sampling over a DecodeSession (static buffers, graph-replayed steps, EOS polled every 8 steps). record = (logits, scores,
-        nb): the per-step raw logits / processed scores are recorded into the session's slots, rows put study-major over nb row groups, and handed
-        out in rec_out as one tuple of [rows, V] tensors per returned step."""
-        dev = self.device
+    @staticmethod
+    def _score_step_kept(logits, ids, cur, plan, tables, got):
+        """score_step_ of a loop without static buffers (_generate_eager, _beam_search): each output `got` has a list for goes to a fresh tensor."""
+        slots = {name: torch.empty(logits.shape, dtype=torch.float32, device=logits.device) for name in got}
+        score_step_(logits, ids, cur, plan, slots.get("logits"), slots.get("scores"), tables)
+        for name, t in slots.items():
+            got[name].append(t)
+
+    def _generate_session(self, ids, enc16, enc_mask8, plan, rec=None, rec_out=None):
+        """Greedy / top-k sampling / the SCST pair over a DecodeSession (static buffers, graph-replayed steps, EOS polled every 8 steps).
+        plan.record: the per-step raw logits / processed scores are recorded into the session's slots, rows put study-major over its row groups,
+        and handed out in rec_out as one tuple of [rows, V] tensors per returned step."""
         B, prompt_len = ids.shape
-        strip = 1 if (self.kind == "longitudinal" and bool(torch.all(ids[:, 0] == bos_token_id))) else 0
+        max_length, eos = plan.max_length, plan.eos
+        strip = 1 if (self.kind == "longitudinal" and bool(torch.all(ids[:, 0] == plan.bos))) else 0
         with torch.no_grad():
             ses = self._session(B, enc16.shape[1], max_length, enc_mask8 is not None, share=B // enc16.shape[0])
-            ses.reset(ids, enc16, enc_mask8)
-            if record is not None:                                   # before any step graph is captured (never from inside a capture)
-                ses.record_buffers(record[0], record[1])
-            if procs is not None and len(procs) > 3:
-                ses.constraint_tables(procs[3])
-            if do_sample == "pair":
-                kind, special = "pair", (tuple(special_token_ids[0]), tuple(special_token_ids[1]))
-            else:
-                kind, special = ("sample" if do_sample else "greedy"), tuple(special_token_ids)
-            mode = (kind, special, mask_token_id, int(top_k or 0), float(temperature), eos_token_id, pad_token_id, bool(self.training), float(top_p),
-                    procs, record)
+            ses.reset(ids, enc16, enc_mask8, plan)
             if rec is not None:
                 rec["seed"] = ses.seed.clone() if self.training else None
                 # the session's cross-attention K / V of every layer (valid until the session's next decode) and the weight version they belong to
                 rec["cross_kv"] = None if ses.cache.kv_all is None else (ses.cache.kv_all, tuple(ses.enc16.shape), self._weights_stamp(), ses, ses.fills)
             cur = prompt_len
             first_tt = first_pos = None
-            poll = None                      # (pinned host word, event): "any row unfinished?" as of the PREVIOUS poll -- read without stalling the queue
             while cur < max_length:
                 # the prefill step alone, then chunks of up to 8 cached steps per graph replay, aligned to the EOS polling period
                 n = 1 if cur == prompt_len else min(8 - (cur - prompt_len) % 8, max_length - cur)
-                ses.step(cur, strip, mode, n)
+                ses.step(cur, strip, plan, n)
                 if rec is not None and cur == prompt_len:            # the prefill step's inputs cover the whole prompt
                     first_tt, first_pos = ses.last_tt.clone(), None if ses.last_pos is None else ses.last_pos.clone()
                 cur += n
-                if eos_token_id is not None and ((cur - prompt_len) % 8 == 0):
-                    # EOS polling every 8 steps, one poll behind: the copy of this poll's flag is only waited for at the NEXT poll, so the host
-                    # keeps enqueueing steps while the GPU works (a blocking .item() drained the queue 32 times per decode); the up to 16 steps of
-                    # overshoot are trimmed below, as the 8 of a blocking poll were
-                    if poll is not None:
-                        poll[1].synchronize()
-                        if int(poll[0][0]) == 0:
-                            break
-                    host = ses.poll_host
-                    host.copy_(ses.unfinished.max().reshape(1), non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    poll = (host, ev)
+                # "any row unfinished?" every 8 steps; the overshoot is trimmed below
+                if eos is not None and (cur - prompt_len) % 8 == 0 and not ses.keep_going(lambda: ses.unfinished.max().reshape(1)):
+                    break
             out = ses.ids[:, :cur].clone()
             if rec is not None:
                 # cached steps appended their token type / position to the session's history columns: ONE copy, then per-step views
@@ -753,21 +809,9 @@ class GenerationMixin:
                     for c in range(th.shape[1]):
                         rec["tt"].append(th[:, c:c + 1])
                         rec["pos"].append(None if ph_ is None else ph_[:, c:c + 1])
-            # HF stops at the step on which the last row finishes: trim what the 8-step polling overshot
-            if eos_token_id is not None:
-                gen = out[:, prompt_len:]
-                is_eos = gen == eos_token_id
-                first = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), gen.shape[1], device=dev))
-                out = out[:, : prompt_len + int(first.max())]
-            if record is not None:                                   # one copy of the returned steps (the session is reused by the next call)
-                self._copy_records(ses, record, prompt_len, out.shape[1] - prompt_len, rec_out)
+            out = trim_at_eos(out, prompt_len, eos)
+            rec_out.update(ses.records(plan.record, prompt_len, out.shape[1] - prompt_len))
         return out
-
-    @staticmethod
-    def _copy_records(ses, record, first, steps, rec_out):
-        for name, buf in zip(("logits", "scores"), ses.record_buffers(record[0], record[1])):
-            if buf is not None:
-                rec_out[name] = buf[first:first + steps].clone().unbind(0)
 
     @torch.no_grad()
     def _weights_stamp(self):
@@ -797,10 +841,7 @@ class GenerationMixin:
         read and every launch. Rows [0,B) are sampled (top-k, temperature) with the separator set `special_sample`, rows [B,2B) take the
         argmax with `special_greedy`; each half sees exactly the per-step inputs its own generate() call would have produced.
         -> (sampled sequences [B,L], greedy sequences [B,L], recorded per-step token-type / position ids of the sampled half)."""
-        enc = encoder_outputs[0]
-        enc_mask = encoder_outputs.get("attention_mask") if isinstance(encoder_outputs, dict) else None
-        if self.kind == "single":
-            enc_mask = None
+        enc, enc_mask = self._encoder_rows(encoder_outputs)
         dev = self.device
         B = enc.shape[0]
         prompt = prompt_ids.to(device=dev, dtype=torch.int64)
@@ -808,22 +849,26 @@ class GenerationMixin:
         first = prompt[:, 0].tolist()                                        # (the one host read of this call: the prompt's first column)
         prepend = all(v != bos_token_id for v in first)
         ids = torch.cat([start, prompt], dim=-1) if prepend else prompt
-        enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
-        enc_mask8 = None if enc_mask is None else enc_mask.to(device=dev, dtype=torch.uint8).contiguous()      # B rows serve the 2B decode rows
+        enc16, enc_mask8 = self._decoder_feed(enc, enc_mask)                 # B rows serve the 2B decode rows
+        plan = StepPlan(kind="pair", special=(tuple(special_sample), tuple(special_greedy)), mask_token_id=mask_token_id, bos=bos_token_id,
+                        eos=eos_token_id, pad=pad_token_id, max_length=max_length, train=bool(self.training), top_k=int(top_k or 0),
+                        temperature=float(temperature), top_p=float(top_p))
         rec = {"tt": [], "pos": []}
-        out = self._generate_session(torch.cat([ids, ids], dim=0), enc16, enc_mask8, (special_sample, special_greedy), mask_token_id,
-                                     max_length, bos_token_id, eos_token_id, pad_token_id, "pair", top_k, temperature, rec, top_p=top_p)
+        out = self._generate_session(torch.cat([ids, ids], dim=0), enc16, enc_mask8, plan, rec, {})
         rec = {"tt": [t[:B] for t in rec["tt"]], "pos": [None if p_ is None else p_[:B] for p_ in rec["pos"]], "seed": rec.get("seed"),
                "cross_kv": rec.get("cross_kv")}
+        # each half ends where ITS last row finished (HF stops per generate() call)
+        return trim_at_eos(out[:B], ids.shape[1], eos_token_id), trim_at_eos(out[B:], ids.shape[1], eos_token_id), rec
 
-        def trim(seq):                                   # each half ends where ITS last row finished (HF stops per generate() call)
-            if eos_token_id is None:
-                return seq
-            gen = seq[:, ids.shape[1]:]
-            is_eos = gen == eos_token_id
-            first = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((B,), gen.shape[1], device=dev))
-            return seq[:, : ids.shape[1] + int(first.max())]
-        return trim(out[:B]), trim(out[B:]), rec
+    def _encoder_rows(self, encoder_outputs):
+        """-> (encoder hidden states, their attention mask | None); the single-image model attends to every row."""
+        enc_mask = encoder_outputs.get("attention_mask") if isinstance(encoder_outputs, dict) else None
+        return encoder_outputs[0], None if self.kind == "single" else enc_mask
+
+    def _decoder_feed(self, enc, enc_mask):
+        """-> the decode kernels' views of the encoder output: bf16 rows (detached) and the mask as bytes."""
+        enc16 = (enc if enc.dtype == torch.bfloat16 else ops.cast_to_bf16(enc.float().contiguous())).detach().contiguous()
+        return enc16, None if enc_mask is None else enc_mask.to(device=self.device, dtype=torch.uint8).contiguous()
 
     generate = torch.no_grad()(_generate)          # `.generate.__wrapped__` is the grad-enabled body (reference scst/gt_prompt.py:162)
 
@@ -891,84 +936,61 @@ class GenerationMixin:
         return tuple(_as_boundary(s_t, kind="step", base=sc, t=t) for t, s_t in enumerate(sc.unbind(1)))
 
     # ------------------------------------------------------------------------------------------ beam search
-    def _beam_search_session(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                             procs=None, n_ret=1, record=None, rec_out=None, es=0):
-        """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False; es: early_stopping as early_stopping_mode() numbers it) over a DecodeSession:
-        beams*B rows decoded by the cached-step kernels (the beams of a study share its cross-attention K/V: ONE copy of the encoder rows, as in
-        the SCST sample+greedy batch), the whole per-step bookkeeping in one kernel launch (ops.beam_step), the cache reorder in another, the
-        steps replayed from hipGraphs eight at a time, and the stop condition polled asynchronously every 8 steps (the stopped state is frozen
-        on the device, so overshoot steps change nothing). The host loop `_beam_search` does the same with ~40 tensor ops and two
-        synchronisations per token. procs: the generation controls, applied to the log-probs (log_softmax, then csrc/logits_proc.hip, then the beam
-        step over the processed log-probs as they are). Returns the n_ret best finished hypotheses of every study, study-major, and their scores.
-        record = (logits, scores): rec_out receives the per-step raw logits / processed log-probs of the steps the search ran ([B * nb, V] each,
-        study-major) and the beam indices of the returned hypotheses (int32 [B * n_ret, generated length]), as TF5 returns them."""
+    def _beam_search_session(self, ids, enc16, enc_mask8, plan, n_ret=1, rec_out=None):
+        """Beam search (TF5 generation/utils.py:3208-3560, do_sample=False; plan.early_stopping as early_stopping_mode() numbers it) over a
+        DecodeSession: beams*B rows decoded by the cached-step kernels (the beams of a study share its cross-attention K/V: ONE copy of the encoder
+        rows, as in the SCST sample+greedy batch), the whole per-step bookkeeping in one kernel launch (ops.beam_step), the cache reorder in
+        another, the steps replayed from hipGraphs eight at a time, and the stop condition polled asynchronously every 8 steps (the stopped state
+        is frozen on the device, so overshoot steps change nothing). The host loop `_beam_search` does the same with ~40 tensor ops and two
+        synchronisations per token. Returns the n_ret best finished hypotheses of every study, study-major, and their scores. plan.record:
+        rec_out receives the per-step raw logits / processed log-probs (score_step_) of the steps the search ran ([B * nb, V] each, study-major)
+        and the beam indices of the returned hypotheses (int32 [B * n_ret, generated length]), as TF5 returns them."""
         B, prompt_len = ids.shape
-        nb = num_beams
-        pad = 0 if pad is None else pad
-        strip = 1 if (self.kind == "longitudinal" and bool(torch.all(ids[:, 0] == bos))) else 0
+        nb, max_length, es = plan.num_beams, plan.max_length, plan.early_stopping
+        strip = 1 if (self.kind == "longitudinal" and bool(torch.all(ids[:, 0] == plan.bos))) else 0
         with torch.no_grad():
             ses = self._session(B * nb, enc16.shape[1], max_length, enc_mask8 is not None, share=nb)
-            ses.reset(ids.repeat(nb, 1), enc16, enc_mask8)
-            ses.ids[:, prompt_len:] = pad
-            st = ses.beam_state(nb, pad, bidx=record is not None, allfin=es == 1)
-            if record is not None:                                   # before any step graph is captured (never from inside a capture)
-                ses.record_buffers(record[0], record[1])
-            if procs is not None and len(procs) > 3:
-                ses.constraint_tables(procs[3])
-            mode = ("beam", tuple(special_token_ids), mask_token_id, nb, float(length_penalty), eos, pad, bool(self.training), (prompt_len, max_length, es),
-                    procs, None if record is None else (record[0], record[1], nb))
+            ses.reset(ids.repeat(nb, 1), enc16, enc_mask8, plan)
+            ses.ids[:, prompt_len:] = plan.pad
+            st = ses.beam_state(nb, plan.pad, bidx=plan.record.on, allfin=es == 1)
+
+            def going():                                                # flags of the last executed step (column cur - 1)
+                par = (cur - 1) & 1
+                flag = (st["unsat"][par].max() > 0) & (st["allhit"][par].min() == 0)
+                if es == 1:                                             # early_stopping=True: every study's finished set is full
+                    flag = flag & (st["allfin"][par].min() == 0)
+                return flag.to(torch.int32).reshape(1)
             cur = prompt_len
-            poll = None
             while cur < max_length:
                 n = 1 if cur == prompt_len else min(8 - (cur - prompt_len) % 8, max_length - cur)
-                ses.step(cur, strip, mode, n)
+                ses.step(cur, strip, plan, n)
                 cur += n
-                if (cur - prompt_len) % 8 == 0 and cur < max_length:
-                    if poll is not None:
-                        poll[1].synchronize()
-                        if int(poll[0][0]) == 0:
-                            break
-                    par = (cur - 1) & 1                                     # flags of the last executed step (column cur - 1)
-                    going = (st["unsat"][par].max() > 0) & (st["allhit"][par].min() == 0)
-                    if es == 1:                                             # early_stopping=True: every study's finished set is full
-                        going = going & (st["allfin"][par].min() == 0)
-                    going = going.to(torch.int32).reshape(1)
-                    ses.poll_host.copy_(going, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    poll = (ses.poll_host, ev)
-            if n_ret == 1:
-                out = st["sequences"][0].clone()
-                scores = st["beam_scores"][:, 0].clone()
-            else:                                                           # the finished set is held best first: [n, B] -> study-major rows
-                out = st["sequences"][:n_ret].transpose(0, 1).reshape(B * n_ret, st["sequences"].shape[2]).clone()
-                scores = st["beam_scores"][:, :n_ret].reshape(-1).clone()
-            if record is not None:
+                if (cur - prompt_len) % 8 == 0 and cur < max_length and not ses.keep_going(going):
+                    break
+            # the finished set is held best first: [n, B] -> study-major rows
+            out = st["sequences"][:n_ret].transpose(0, 1).reshape(B * n_ret, st["sequences"].shape[2]).clone()
+            scores = st["beam_scores"][:, :n_ret].reshape(-1).clone()
+            if plan.record.on:
                 # steps the search ran (later launches are frozen): every running beam has a parent in each of their columns
                 steps = int((st["run_bidx"][0, 0, prompt_len:] >= 0).sum())
-                self._copy_records(ses, (record[0], record[1]), prompt_len, steps, rec_out)
+                rec_out.update(ses.records(plan.record, prompt_len, steps))
                 bidx = st["fin_bidx"][:n_ret].transpose(0, 1).reshape(B * n_ret, -1)[:, prompt_len:]
                 rec_out["beam_indices"] = self._trim_beam_indices(bidx)
-        if eos is None:
-            return out, scores
-        gen = out[:, prompt_len:]
-        is_eos = gen == eos
-        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((out.shape[0],), gen.shape[1], device=out.device))
-        return out[:, : prompt_len + int(lens.max())], scores
+        return trim_at_eos(out, prompt_len, plan.eos), scores
 
     @staticmethod
     def _trim_beam_indices(bidx):
         """TF5:gen:3517-3523: the history columns up to the longest returned hypothesis."""
         return bidx[:, :int((bidx >= 0).sum(1).max())].clone()
 
-    def _beam_search(self, ids, enc16, enc_mask8, special_token_ids, mask_token_id, max_length, num_beams, bos, eos, pad, length_penalty,
-                     procs=None, n_ret=1, record=None, rec_out=None, es=0):
-        """TF5 generation/utils.py:3208-3560 with do_sample=False, one EOS id, early_stopping False / True / "never" (es = 0 / 1 / 2,
+    def _beam_search(self, ids, enc16, enc_mask8, plan, n_ret=1, rec_out=None):
+        """TF5 generation/utils.py:3208-3560 with do_sample=False, one EOS id, early_stopping False / True / "never" (plan.early_stopping = 0 / 1 / 2,
         early_stopping_mode()); the n_ret best hypotheses per study.
-        record / rec_out as in _beam_search_session, with the beam-index histories kept by torch ops."""
+        plan.record / rec_out as in _beam_search_session (one row group: the rows are study-major), the beam-index histories kept by torch ops."""
         dev = ids.device
         B = ids.shape[0]
-        nb, keep = num_beams, 2 * num_beams
+        nb, keep = plan.num_beams, 2 * plan.num_beams
+        eos, pad, max_length, es, length_penalty, record = plan.eos, plan.pad, plan.max_length, plan.early_stopping, plan.length_penalty, plan.record.on
         V = self.config.decoder.vocab_size
         ids = ids.repeat_interleave(nb, dim=0)
         enc16 = enc16.repeat_interleave(nb, dim=0).contiguous()
@@ -986,11 +1008,11 @@ class GenerationMixin:
         batch_off = (torch.arange(B, device=dev) * nb).view(B, 1)
         cache = self._dec.new_cache(B * nb, max_length, dev)
         seed = self.next_dropout_seed() if self.training else None
-        tables = constraint_tables(procs[3], dev) if procs is not None and len(procs) > 3 else None
-        if record is not None:                                     # beam-index histories (TF5:gen:3348-3351), absolute token columns
+        tables = constraint_tables(plan.controls.cons, dev) if plan.controls.constrained else None
+        got = {name: [] for name in RECORDED if getattr(plan.record, name)}
+        if record:                                                 # beam-index histories (TF5:gen:3348-3351), absolute token columns
             run_bidx = torch.full((B, nb, max_length), -1, dtype=torch.int32, device=dev)
             fin_bidx = run_bidx.clone()
-            got = {"logits": [], "scores": []}
 
         def gather(t, idx):
             while idx.dim() < t.dim():
@@ -999,25 +1021,15 @@ class GenerationMixin:
 
         while True:
             flat = running[:, :, :cur].reshape(B * nb, cur)
-            fed = self._fed(flat, bos)
-            new, mask, tt, pos = self._step_inputs(fed, special_token_ids, mask_token_id, prefill=cache.len == 0)
+            fed = self._fed(flat, plan.bos)
+            new, mask, tt, pos = self._step_inputs(fed, plan.special, plan.mask_token_id, prefill=cache.len == 0)
             logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
                                       seed=seed)
-            if record is not None and (record[0] or procs is None):           # raw logits; without processors the log-probs in the same pass
-                lo = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if record[0] else None
-                so = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if record[1] and procs is None else None
-                ops.gen_record(logits, lo, so, log_softmax=True)
-                for k, t in (("logits", lo), ("scores", so)):
-                    if t is not None:
-                        got[k].append(t)
-            if procs is None:
-                ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
-            else:                                                                             # processors act on the log-probs (TF5:gen:3388-3389)
-                ops.log_softmax_rows_(logits)
-                process_scores_(logits, flat.contiguous(), cur, -1 if eos is None else eos, procs, tables)
-                if record is not None and record[1]:
-                    got["scores"].append(ops.gen_record(logits, None, torch.empty(logits.shape, dtype=torch.float32, device=logits.device))[1])
+            self._score_step_kept(logits, flat.contiguous(), cur, plan, tables, got)
+            if plan.controls.active:                                                          # processed log-probs (TF5:gen:3388-3389) + running beam score
                 logits.add_(run_scores.view(-1, 1))
+            else:
+                ops.log_softmax_rows_(logits, add_row=run_scores.view(-1).contiguous())          # log_softmax + running beam score
             topk_lp, topk_idx = ops.topk_rows(logits.view(B, nb * V), keep)
             beam_of = topk_idx // V
             topk_seq = gather(running, beam_of)
@@ -1027,7 +1039,7 @@ class GenerationMixin:
             nxt = torch.topk(run_lp, k=nb)[1]
             running, run_scores = gather(topk_seq, nxt), gather(run_lp, nxt)
             beam_idx = (gather(beam_of, nxt) + batch_off).view(-1)
-            if record is not None:                                  # TF5:gen:3116-3127, :3150
+            if record:                                              # TF5:gen:3116-3127, :3150
                 topk_bidx = gather(run_bidx, beam_of)
                 topk_bidx[:, :, cur] = (beam_of + batch_off).to(torch.int32)
                 run_bidx = gather(topk_bidx, nxt)
@@ -1041,7 +1053,7 @@ class GenerationMixin:
             m_fin = torch.cat((finished, just), dim=1)
             best = torch.topk(m_sc, k=nb)[1]
             sequences, beam_scores, finished = gather(m_seq, best), gather(m_sc, best), gather(m_fin, best)
-            if record is not None:                                  # TF5:gen:3197-3202
+            if record:                                              # TF5:gen:3197-3202
                 fin_bidx = gather(torch.cat((fin_bidx, topk_bidx), dim=1), best)
             cache.reorder(beam_idx.contiguous())
             cur += 1
@@ -1052,14 +1064,7 @@ class GenerationMixin:
                 break
         out = sequences[:, 0, :] if n_ret == 1 else sequences[:, :n_ret, :].reshape(B * n_ret, -1)
         sc = beam_scores[:, 0] if n_ret == 1 else beam_scores[:, :n_ret].reshape(-1)
-        if record is not None:
-            for k, want in zip(("logits", "scores"), record):
-                if want:
-                    rec_out[k] = tuple(got[k])
+        if record:
+            rec_out.update({name: tuple(kept) for name, kept in got.items()})
             rec_out["beam_indices"] = self._trim_beam_indices(fin_bidx[:, :n_ret, prompt_len:].reshape(B * n_ret, -1))
-        if eos is None:
-            return out, sc
-        gen = out[:, prompt_len:]
-        is_eos = gen == eos
-        lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full((out.shape[0],), gen.shape[1], device=dev))
-        return out[:, : prompt_len + int(lens.max())], sc
+        return trim_at_eos(out, prompt_len, eos), sc

@@ -2,6 +2,7 @@
 cxr_beam_step_es), the option validation of generate() (the library's messages), the merge of a generation_config object, and the CPU restatement
 of the early-stopping beam search against the reference's recorded searches (tests/golden/gen_constraints.npz)."""
 import ctypes
+import dataclasses
 from types import SimpleNamespace
 
 import numpy as np
@@ -122,6 +123,76 @@ def test_token_constraints_description():
     assert gen.token_constraints(1000, gu.EOS, 1, 20, begin_suppress_tokens=[8])[-1] == 1
     assert gen.token_constraints(1000, gu.EOS, 6, 20, begin_suppress_tokens=[8], forced_bos_token_id=6)[-1] == 6
     hash(c)
+
+
+# ------------------------------------------------------------------------------------------------ the step plan (graph cache key)
+def a_plan(bias=0.5, **kw):
+    """A plan with every field away from its default, over a freshly built constraint description."""
+    c = cons(sequence_bias=[[[5, 6], bias], [[7], -1.0]], bad_words_ids=[[3, gu.EOS]], suppress_tokens=[4], begin_suppress_tokens=[8],
+             forced_bos_token_id=6, forced_eos_token_id=[gu.EOS])
+    f = dict(kind="beam", special=(gu.SEP, gu.BOS), mask_token_id=gu.PAD, bos=gu.BOS, eos=gu.EOS, pad=gu.PAD, max_length=20, train=True,
+             controls=gen.Controls(1.3, 3, 9, c), record=gen.Record(True, True, 4), top_k=5, temperature=0.7, top_p=0.9, num_beams=4,
+             length_penalty=2.0, prompt_len=3, early_stopping=2)
+    f.update(kw)
+    return gen.StepPlan(**f)
+
+
+def changed(v):
+    """Another value of v's own type: the first leaf of a (named) tuple is changed."""
+    if isinstance(v, bool):
+        return not v
+    if isinstance(v, (int, float)):
+        return v + 1
+    if isinstance(v, str):
+        return v + "x"
+    if isinstance(v, tuple):
+        head = (changed(v[0]),) + tuple(v[1:]) if v else (1,)
+        return type(v)(*head) if hasattr(v, "_fields") else head
+    assert v is None, v
+    return 0
+
+
+def test_equal_options_give_equal_plans():
+    a, b = a_plan(), a_plan()
+    assert a.controls.cons is not b.controls.cons                        # two token_constraints() calls: equal, distinct descriptions
+    assert a == b and hash(a) == hash(b)
+    assert {(7, 8, 0, a): "graph"}[(7, 8, 0, b)] == "graph"              # the captured step of the first call is found by the second
+
+
+@pytest.mark.parametrize("field", [f.name for f in dataclasses.fields(gen.StepPlan)])
+def test_any_changed_field_gives_an_unequal_plan(field):
+    a = a_plan()
+    v = getattr(a, field)
+    b = dataclasses.replace(a, **{field: changed(v)})
+    assert a != b and (7, 8, 0, b) not in {(7, 8, 0, a): "graph"}
+    if hasattr(v, "_fields"):                                            # every leaf of the controls / the record request counts
+        for name in v._fields:
+            assert dataclasses.replace(a, **{field: v._replace(**{name: changed(getattr(v, name))})}) != a, (field, name)
+
+
+def test_one_sequence_bias_entry_changes_the_plan():
+    a, b = a_plan(), a_plan(bias=0.25)
+    assert a.controls.cons[0][0] == ((5, 6), 0.5) and b.controls.cons[0][0] == ((5, 6), 0.25)
+    assert a != b and (7, 8, 0, b) not in {(7, 8, 0, a): "graph"}
+
+
+def test_plan_refuses_values_compared_by_identity():
+    for bad in ([gu.SEP], torch.tensor([gu.SEP]), {gu.SEP: 1}, ([gu.SEP],), len):
+        with pytest.raises(TypeError):
+            a_plan(special=bad)
+    with pytest.raises(TypeError):
+        a_plan(controls=gen.Controls(1.3, 3, 9, ([((5, 6), 0.5)],)))           # a list nested in the constraints
+    with pytest.raises(TypeError):
+        a_plan(eos=torch.tensor(gu.EOS))
+
+
+def test_controls_say_what_a_step_launches():
+    assert not gen.Controls().active and not gen.Controls().constrained
+    for c in (gen.Controls(penalty=1.3), gen.Controls(ngram=2), gen.Controls(min_abs=5)):
+        assert c.active and not c.constrained
+    c = gen.Controls(cons=cons(suppress_tokens=[4]))
+    assert c.active and c.constrained
+    assert not gen.Record().on and gen.Record(logits=True).on and gen.Record(scores=True).on
 
 
 # ------------------------------------------------------------------------------------------------ generation_config

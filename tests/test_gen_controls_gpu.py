@@ -268,6 +268,55 @@ def test_defaults_launch_nothing_new(M, G, monkeypatch):
     assert b3.shape[0] == 3
 
 
+REPLAY_CASES = {"greedy": dict(num_beams=1), "sample": dict(num_beams=1, do_sample=True, top_k=5), "beam": dict(num_beams=4),
+                "beam_early": dict(num_beams=4, early_stopping=True),
+                "controls": dict(num_beams=1, repetition_penalty=1.3, suppress_tokens=[7]),
+                "records": dict(num_beams=1, return_dict_in_generate=True, output_logits=True, output_scores=True)}
+
+
+@pytest.fixture(scope="module")
+def replay_model(M, G):
+    return multi_model(M, G, "beam")
+
+
+@pytest.mark.parametrize("case", list(REPLAY_CASES))
+def test_a_repeated_call_replays_its_graphs(replay_model, case):
+    """Equal options must find the step graphs of the call before (a plan compared by identity would capture every step again on every call and pass
+    every other test); one changed option must not find them. max_length 11 over the one-token prompt: the eager prefill, one 7-step graph, one
+    stop poll, one 2-step graph."""
+    m, kw = replay_model
+    o = REPLAY_CASES[case]
+
+    def run(o):
+        torch.manual_seed(77)
+        out = m.generate(**{**kw, **o}, max_length=11)
+        keys = [set(s_.graphs) for s_ in m._decode_sessions.values()]
+        return (out if torch.is_tensor(out) else out["sequences"]).cpu(), set().union(*keys)
+    m.__dict__.pop("_decode_sessions", None)                             # this case's graphs only
+    first, keys = run(o)
+    assert keys and {k[:2] for k in keys} == {(2, 7), (9, 2)}            # (column, steps) behind the eager prefill of column 1
+    assert {k[3].kind for k in keys} == {"beam" if o["num_beams"] > 1 else "sample" if "do_sample" in o else "greedy"}
+    second, keys2 = run(o)
+    assert keys2 == keys                                                 # nothing was captured again
+    assert torch.equal(second, first)
+    if "top_k" in o:
+        other = dict(o, top_k=6)
+    elif "suppress_tokens" in o:
+        other = dict(o, suppress_tokens=[8])
+    elif "early_stopping" in o:
+        other = dict(o, early_stopping=False)
+    elif "output_logits" in o:
+        other = dict(o, output_logits=False)
+    elif case == "beam":
+        other = dict(o, length_penalty=2.0)
+    else:
+        other = dict(o, pad_token_id=gu.PAD + 1)
+    _, keys3 = run(other)
+    added = keys3 - keys
+    assert keys <= keys3 and added and {k[:3] for k in added} == {k[:3] for k in keys}      # the same steps, captured anew under another plan
+    assert not {k[3] for k in added} & {k[3] for k in keys}
+
+
 def test_invalid_options_raise(M, G):
     m, kw = multi_model(M, G, "beam")
     with pytest.raises(ValueError):

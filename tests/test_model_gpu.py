@@ -1232,7 +1232,7 @@ def test_device_beam_search_full_size_fused_steps(M):
     s = d1["sequences"]
     assert s.shape[0] == 2 and bool((s[:, 0] == gu.BOS).all()) and s.shape[1] <= 20 and int(s.max()) < cfg.decoder.vocab_size
     ses = [v for k, v in m._decode_sessions.items() if k[-1] == 4]
-    assert ses and any(k[0] == "beam" for s_ in ses for (_, _, _, k) in s_.graphs)          # the steps were replayed from captured graphs
+    assert ses and any(k.kind == "beam" for s_ in ses for (_, _, _, k) in s_.graphs)          # the steps were replayed from captured graphs
 
 
 def test_single_image_model_generate_matches_the_reference(M):
