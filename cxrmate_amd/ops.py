@@ -1765,3 +1765,33 @@ def coco_nlg_scores(ids_a, off_a, ids_b, off_b, pairs, ref_mult, order, study_of
     LIB.call("cxr_coco_nlg_scores", _p(ids_a), ids_a.shape[0], _p(off_a), _p(ids_b), ids_b.shape[0], _p(off_b), n_texts, _p(pairs), _p(ref_mult),
              M, _p(order), _p(study_off), S, _p(scores), _p(ints), _p(study), _p(avg), _p(ws), ws.numel() * 8, _s())
     return scores, ints, study, avg
+
+
+IMAGE_TRANSFORM_DESC_INTS = 24
+IMAGE_TRANSFORM_BAND_BYTES = 49152
+
+
+def image_transform_workspace_bytes(inter):
+    """Bytes of workspace cxr_image_transform needs: `inter` lists (H, ow, C) of every image -- source rows, resized width, channels -- whose
+    uint8 intermediate [H, ow, C] of the horizontal pass starts at a multiple of 16 (the formula in its header comment)."""
+    return sum((int(h) * int(ow) * int(c) + 15) // 16 * 16 for h, ow, c in inter)
+
+
+def image_transform(src, desc, tables, n_images, n_bands, B, Nmax, S, mean, std, inter_bytes, want_f32=True, want_u8=False):
+    """Resize + crop + rotation + normalise + pad of a packed batch of decoded images (see cxr_image_transform and pixels.StudyImageTransform,
+    which builds the arguments). src uint8 [bytes]; desc int32 = descriptors + slot map + band table; tables int32. -> (fp32 [B, Nmax, 3, S, S]
+    or None, uint8 [n_images, S, S, 3] or None)."""
+    assert src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()
+    for t in (desc, tables):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()
+    if not (src.is_cuda and desc.is_cuda and tables.is_cuda):
+        raise CxrError("image_transform runs on the device: host tensors are refused (cxrmate_amd has no CPU / PyTorch fallback)")
+    assert desc.device == src.device and tables.device == src.device
+    assert desc.numel() == n_images * IMAGE_TRANSFORM_DESC_INTS + B * Nmax + 2 * n_bands
+    dev = src.device
+    out = torch.empty((B, Nmax, 3, S, S), dtype=torch.float32, device=dev) if want_f32 else None
+    u8 = torch.empty((n_images, S, S, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+    ws = torch.empty((max(int(inter_bytes), 16),), dtype=torch.uint8, device=dev)
+    LIB.call("cxr_image_transform", _p(src), src.numel(), _p(desc), n_images, n_bands, _p(tables), tables.numel(), B, Nmax, S,
+             *[float(m) for m in mean], *[float(s) for s in std], _p(out), _p(u8), _p(ws), ws.numel(), int(inter_bytes), _s())
+    return out, u8

@@ -485,6 +485,25 @@ int cxr_gather_batch_multi_bf16(const void* const* in, void* const* out, int n, 
 int cxr_pixels_u8_to_f32(const void* src, const long* first_image, float* dst, int B, int Nmax, int H, int W, float mean0, float mean1,
                          float mean2, float std0, float std1, float std2, hipStream_t stream);
 
+/* ---- input pipeline transforms (next-row f3; REF:modules/lightning_modules/single.py:229-262): Resize(S) + CenterCrop(S) (test) or RandomCrop(S) +
+ * RandomRotation (train) + ToTensor + Normalize + pad_sequence from the DECODED full-size uint8 images, byte-identical to Pillow's antialiased
+ * bilinear Image.resize and nearest-neighbour Image.rotate (integer arithmetic only; the host builds the tables: cxrmate_amd/pixels.py).
+ * src: the images packed into one buffer, grey [H][pitch] or interleaved RGB, each at a 16-byte aligned offset with a row pitch that is a multiple
+ * of 16 and at most 49152 bytes. desc int32: [n_images][24] descriptors, then slot_image [B*Nmax] (the image of slot [b, n], -1 = absent), then
+ * bands [n_bands][2] = (image, first source row) of every workgroup of the horizontal pass (rows 0, r, 2r, ... with r = 49152 / pitch).
+ * Descriptor: 0 source offset / 16, 1 H, 2 W, 3 C (1 or 3), 4 pitch, 5 oh, 6 ow (resized size), 7 top, 8 left (crop), 9 / 10 horizontal table
+ * offset into `tables` and its ksize, 11 / 12 the vertical table's, 13 intermediate offset / 16 in the workspace (uint8 [H][ow][C]), 14-15 unused,
+ * 16-21 a0..a5: output pixel (x, y) of the S x S crop reads crop pixel ((a2 + a1 y + a0 x) >> 16, (a5 + a4 y + a3 x) >> 16), 0 outside (Pillow's
+ * affine_fixed; the identity is 65536, 0, 32768, 0, 65536, 32768), 22-23 unused. Table of an (in -> out) axis: bounds int32 [out][2] = (first
+ * tap, taps), then weights int32 [ksize][out] with 22 fractional bits; a sample is clip8((2^21 + sum src * weight) >> 22).
+ * -> out_f32 [B][Nmax][3][S][S] = u * (1/(255 std)) - mean/std, absent slots 0.0, and / or out_u8 [n_images][S][S][3]; either may be null, not
+ * both. workspace: inter_bytes = the sum over the images of H * ow * C rounded up to 16, 16-byte aligned; workspace_bytes < inter_bytes returns -1.
+ * A descriptor that does not fit the buffers as passed gives that image NaN (fp32) / 0 (uint8) and is never followed; tap ranges are clamped to
+ * their rows. Two launches whatever n_images is; no atomics: repeated launches are bit-identical. */
+int cxr_image_transform(const void* src, long src_bytes, const int* desc, int n_images, int n_bands, const int* tables, long n_table_ints,
+                        int B, int Nmax, int S, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                        float* out_f32, void* out_u8, void* workspace, long workspace_bytes, long inter_bytes, hipStream_t stream);
+
 /* ---- CheXbert labeller heads (next-row f4; REF:tools/chexbert.py:74-81): out[r][s] = argmax over columns [offsets[s], offsets[s+1]) of
  * the stacked head logits (lowest index wins ties, like torch.argmax); offsets int32 [nseg+1], out int64 [R][nseg]. */
 int cxr_segment_argmax_f32(const float* x, long ld, const int* offsets, int nseg, long* out, long R, hipStream_t stream);
