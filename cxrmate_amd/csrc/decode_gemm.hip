@@ -373,6 +373,9 @@ extern "C" int cxr_dec_gemm_bf16(const cxr_dec_gemm_desc* d, hipStream_t stream)
         if (q.N < 16 || (q.N % 2) || !q.Wp || !q.bc || !q.C || (q.lr_Ap && !q.lr_B) || (q.fold && !d->stats)) return CXR_ERR_ARG;
         if (!q.c_dal && (q.ldc % 2)) return CXR_ERR_ARG;
         if (q.c_dal && d->out_f32) return CXR_ERR_ARG;
+        // the decode activation layout is made of 32-column blocks: with a half-filled last block and more than one row tile, dal_off() of the last
+        // rows lies past an [16 * tiles, N] buffer
+        if ((q.N % 32) && (q.c_dal || (i == 0 && d->residual && d->ldr == 0))) return CXR_ERR_ARG;
         DecProb& P = g.p[i];
         P.Wp = (const bf16_t*)q.Wp; P.bc = (const float2*)q.bc; P.C = q.C; P.ldc = q.ldc; P.N = q.N; P.lr_site = q.lr_site; P.c_dal = q.c_dal ? 1u : 0u;
         P.lr_Ap = q.lr_Ap ? (const bf16_t*)q.lr_Ap : (const bf16_t*)dummy; P.lr_B = q.lr_B ? (const bf16_t*)q.lr_B : (const bf16_t*)dummy;

@@ -265,7 +265,12 @@ __global__ __launch_bounds__(C::THREADS, (C::OCC * C::WM * C::WN + 3) / 4) void 
                 for (int nt = 0; nt < NT; ++nt) acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[kk][nt], fa[kk][mt], acc[nt][mt], 0, 0, 0);
                 if (kk + 1 < KK) {
                     fa[kk + 1][mt] = *reinterpret_cast<const bf16x8_t*>(st + fragA + mt * 16 * C::ROWB + chk[kk + 1 < KK ? kk + 1 : 0]);
-                    if (mt < NT) fw[kk + 1][mt] = *reinterpret_cast<const bf16x8_t*>(st + fragW + ((mt >> 1) * 32 + (mt & 1) * 4) * C::ROWB + chk[kk + 1 < KK ? kk + 1 : 0]);
+                    // the NT W fragments of the second half, dealt to the MT groups: one each to the first NT groups, or NT / MT per group where a
+                    // wave has fewer A fragments than W fragments (MT = 2: the 32-row wave tile)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        if ((MT >= NT ? t : t * MT / NT) == mt)
+                            fw[kk + 1][t] = *reinterpret_cast<const bf16x8_t*>(st + fragW + ((t >> 1) * 32 + (t & 1) * 4) * C::ROWB + chk[kk + 1 < KK ? kk + 1 : 0]);
                 }
                 if constexpr (ISSUE) {
                     // pieces p with p * GROUPS / LPS == gi: evenly spread, the first right behind the first group
