@@ -62,6 +62,56 @@ class SharedCrossKV:
                                "cross_kv=None to project K / V again")
 
 
+class StepRecord:
+    """What a cached step records beside its logits (output_attentions / output_hidden_states of generate and of forward(past_key_values=)), and
+    where. attn / hidden: which of the two. Eager callers read the lists afterwards, one fresh fp32 tensor per layer as BertEngine.forward's
+    `collect` gives them: self_attn [rows, H, Tn, past + Tn], cross_attn [rows, H, Tn, S], hidden (L + 1 entries) [rows, Tn, D]. A decode session
+    passes its static slots of the step instead (single-token steps only; a prefill always returns fresh tensors): self_slot fp32
+    [L, rows, H, Lmax], cross_slot [L, rows, H, S], hidden_slot [L + 1, rows, D] -- the kernels write into them and the lists stay empty.
+    row_groups: decode row g * (rows // row_groups) + s is stored as row s * row_groups + g (study-major)."""
+
+    def __init__(self, attn=False, hidden=False, self_slot=None, cross_slot=None, hidden_slot=None, row_groups=1):
+        self.attn, self.hidden_on, self.row_groups = bool(attn), bool(hidden), int(row_groups)
+        self.self_slot, self.cross_slot, self.hidden_slot = self_slot, cross_slot, hidden_slot
+        self.self_attn, self.cross_attn, self.hidden = [], [], []
+
+    def _study_major(self, t):
+        g = self.row_groups
+        return t if g == 1 else t.view(g, t.shape[0] // g, *t.shape[1:]).transpose(0, 1).reshape(t.shape)
+
+    def put_attn(self, kind, l, p):
+        """a fresh map [rows, H, Tn, Tk] in decode row order (prefill, or a step whose attention is the tiled kernel)"""
+        slot = self.self_slot if kind == "self" else self.cross_slot
+        p = self._study_major(p)
+        if slot is not None and p.shape[2] == 1:
+            slot[l][:, :, :p.shape[3]].copy_(p[:, :, 0, :])
+        else:
+            (self.self_attn if kind == "self" else self.cross_attn).append(p)
+
+    def decode_probs(self, kind, l, q, k, heads, scale, **kw):
+        """the map of a single-query attention launch, by the kernel of csrc/attn_decode_probs.hip, into the slot or a fresh tensor"""
+        slot = self.self_slot if kind == "self" else self.cross_slot
+        out = None if slot is None else slot[l][:, :, :k.shape[1]]
+        p = ops.attention_decode_probs(q, k, heads, scale, out=out, row_groups=self.row_groups, **kw)
+        if slot is None:
+            (self.self_attn if kind == "self" else self.cross_attn).append(p)
+
+    def put_hidden(self, i, h, B, Tn):
+        """state i (0: embedding output) as row-major bf16 [B * Tn, D]: widened, as BertEngine.forward does"""
+        f = self._study_major(ops.cast_to_f32(h).view(B, Tn, -1))
+        if self.hidden_slot is not None and Tn == 1:
+            self.hidden_slot[i].copy_(f[:, 0, :])
+        else:
+            self.hidden.append(f)
+
+    def hidden_dal(self, i, x, B, gamma=None, beta=None, eps=0.0):
+        """state i of a fused step from its decode-activation-layout rows (LayerNorm(gamma, beta) of them, or as they are)"""
+        out = None if self.hidden_slot is None else self.hidden_slot[i]
+        f = ops.dec_hidden_record(x, B, gamma, beta, eps, out=out, row_groups=self.row_groups)
+        if self.hidden_slot is None:
+            self.hidden.append(f.view(B, 1, -1))
+
+
 class KVCache:
     """Per-layer self-attention K/V [B, Tmax, D] (appended in place) and cross-attention K/V [B, S, D] (projected once)."""
 
@@ -630,8 +680,9 @@ class BertEngine:
     def new_cache(self, B, Tmax, device):
         return KVCache(self.cfg.num_hidden_layers, B, Tmax, self.cfg.hidden_size, device)
 
-    def decode(self, cache: KVCache, ids_new, enc, enc_mask, attn_mask_full, token_type_ids, position_ids, train=None, seed=None):
-        """One cached step. ids_new [B,Tn] (Tn = prompt length at prefill, 1 afterwards); attn_mask_full uint8 [B, len+Tn] | None.
+    def decode(self, cache: KVCache, ids_new, enc, enc_mask, attn_mask_full, token_type_ids, position_ids, train=None, seed=None, extra=None):
+        """One cached step. extra: None | a StepRecord naming what to record beside the logits (attention maps, hidden states) and where; it only
+        ADDS launches (the step's own are the ones of a call without it: logits and KV cache are bit-identical). ids_new [B,Tn] (Tn = prompt length at prefill, 1 afterwards); attn_mask_full uint8 [B, len+Tn] | None.
         Returns fp32 logits of the LAST position [B, V] (TF5 generation/utils.py:2894). In train mode (the reference decodes under
         model.train() inside its SCST training_step) the dropout masks are keyed by (sequence, ABSOLUTE position), so a later
         teacher-forced pass with the same `seed` reproduces exactly the network that sampled."""
@@ -653,7 +704,10 @@ class BertEngine:
         scale = cfg.head_dim ** -0.5
         pl, ls = float(cfg.lora_dropout), (cfg.lora_alpha / cfg.lora_r if cfg.lora_r else 0.0)
         if fused:
-            return self._decode_single_fused(cache, h, B, enc_mask, attn_mask_full, past, ph, pa, seed, lora_tr)
+            return self._decode_single_fused(cache, h, B, enc_mask, attn_mask_full, past, ph, pa, seed, lora_tr, extra=extra)
+        want_attn, want_hidden = extra is not None and extra.attn, extra is not None and extra.hidden_on
+        if want_hidden:
+            extra.put_hidden(0, h, B, Tn)
         lin = (lambda x, w, **kw: ops.gemm_skinny(x, w, **kw)) if single else (lambda x, w, **kw: ops.gemm_nt(x, w, **kw))
 
         def out_lin(x, w, b, resid, site):
@@ -693,8 +747,14 @@ class BertEngine:
             kk, vv = cache.k[l][:, :past + Tn, :], cache.v[l][:, :past + Tn, :]
             if single:
                 ctx = ops.attention_decode(q, kk, vv, nh, scale, kpm=attn_mask_full, drop=(pa, seed, _site(l, 0), past))
+                if want_attn:
+                    extra.decode_probs("self", l, q, kk, nh, scale, kpm=attn_mask_full, drop=(pa, seed, _site(l, 0), past))
             else:
-                ctx, _ = ops.attention(q, kk, vv, nh, scale, kpm=attn_mask_full, causal=True, causal_shift=past, drop=(pa, seed, _site(l, 0), past))
+                ctx, lse = ops.attention(q, kk, vv, nh, scale, kpm=attn_mask_full, causal=True, causal_shift=past, need_lse=want_attn,
+                                         drop=(pa, seed, _site(l, 0), past))
+                if want_attn:
+                    extra.put_attn("self", l, ops.attention_probs(q, kk, lse, nh, scale, kpm=attn_mask_full, causal=True, causal_shift=past,
+                                                                  drop=(pa, seed, _site(l, 0), past)))
             wo, bo = self._lin(lp + "attention.output.dense")
             a1 = out_lin(ctx.view(R, D), wo, bo, h, _site(l, 1))
             h1, _ = ops.layernorm(a1, st.f32(lp + "attention.output.LayerNorm.weight"), st.f32(lp + "attention.output.LayerNorm.bias"), cfg.layer_norm_eps)
@@ -720,14 +780,25 @@ class BertEngine:
                 q2 = lin(h1, cq, bias=cbq).view(B, Tn, D)
                 if single:
                     ctx2 = ops.attention_decode(q2, cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past))
+                    if want_attn:
+                        extra.decode_probs("cross", l, q2, cache.ck[l], nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past))
                 elif enc.shape[0] == B:
-                    ctx2, _ = ops.attention(q2, cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past))
+                    ctx2, lse2 = ops.attention(q2, cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, need_lse=want_attn, drop=(pa, seed, _site(l, 2), past))
+                    if want_attn:
+                        extra.put_attn("cross", l, ops.attention_probs(q2, cache.ck[l], lse2, nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past)))
                 else:                                  # shared encoder rows (sample + greedy halves of one SCST step): one pass per half
                     ctx2 = torch.empty((B, Tn, D), dtype=BF16, device=h.device)
                     Bk = enc.shape[0]
+                    p2 = torch.empty((B, nh, Tn, S), dtype=torch.float32, device=h.device) if want_attn else None
                     for g0 in range(0, B, Bk):
-                        ops.attention(q2[g0:g0 + Bk], cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, out=ctx2[g0:g0 + Bk],
-                                      drop=(pa, seed, _site(l, 2), past))
+                        # (the dropout hash is keyed by the row WITHIN the launch: each half's maps take the keys its own launch used)
+                        _, lse2 = ops.attention(q2[g0:g0 + Bk], cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, out=ctx2[g0:g0 + Bk],
+                                                need_lse=want_attn, drop=(pa, seed, _site(l, 2), past))
+                        if want_attn:
+                            ops.attention_probs(q2[g0:g0 + Bk], cache.ck[l], lse2, nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past),
+                                                out=p2[g0:g0 + Bk])
+                    if want_attn:
+                        extra.put_attn("cross", l, p2)
                 a2 = out_lin(ctx2.view(R, D), co, cbo, h1, _site(l, 3))
                 h2, _ = ops.layernorm(a2, st.f32(lp + "crossattention.output.LayerNorm.weight"), st.f32(lp + "crossattention.output.LayerNorm.bias"),
                                       cfg.layer_norm_eps)
@@ -737,6 +808,8 @@ class BertEngine:
             f = lin(h2, w1, bias=b1, act=1)
             a3 = out_lin(f, w2, b2, h2, _site(l, 4))
             h, _ = ops.layernorm(a3, st.f32(lp + "output.LayerNorm.weight"), st.f32(lp + "output.LayerNorm.bias"), cfg.layer_norm_eps)
+            if want_hidden:
+                extra.put_hidden(l + 1, h, B, Tn)
         cache.len = past + Tn
         if past == 0:
             cache.cross_ready = True
@@ -816,12 +889,12 @@ class BertEngine:
         return (st.w16(e + "word_embeddings.weight"), st.w16(e + "token_type_embeddings.weight"), st.w16(e + "position_embeddings.weight"),
                 st.f32(e + "LayerNorm.weight"), st.f32(e + "LayerNorm.bias"), self.cfg.layer_norm_eps)
 
-    def decode_embedded(self, cache, x0, B, enc_mask, attn_mask_full, train=None, seed=None):
+    def decode_embedded(self, cache, x0, B, enc_mask, attn_mask_full, train=None, seed=None, extra=None):
         """A cached one-token step whose embedding output x0 (decode activation layout) already exists (ops.decode_step_embed: the step-input
         assembly and the embeddings are one launch). Same result as decode()."""
         self.prepare()
         ph, pa, seed = self._dropout_cfg(train, seed)
-        return self._decode_single_fused(cache, x0, B, enc_mask, attn_mask_full, cache.len, ph, pa, seed, self._lora_train(train))
+        return self._decode_single_fused(cache, x0, B, enc_mask, attn_mask_full, cache.len, ph, pa, seed, self._lora_train(train), extra=extra)
 
     def refresh_decode_packs(self, train=None):
         """Bring the packed decode weights up to the current weight version / train mode (in place). Graph-replayed decode steps do not run
@@ -830,11 +903,14 @@ class BertEngine:
         if self.fuse_decode_layernorm and cfg.hidden_size == 768 and cfg.intermediate_size == 3072 and cfg.add_cross_attention and cfg.vocab_size % 2 == 0:
             self._decode_packs(self._lora_train(train))
 
-    def _decode_single_fused(self, cache, x0, B, enc_mask, attn_mask_full, past, ph, pa, seed, lora_tr=False):
+    def _decode_single_fused(self, cache, x0, B, enc_mask, attn_mask_full, past, ph, pa, seed, lora_tr=False, extra=None):
         """One new token per row on the decode-step kernels of csrc/decode_gemm.hip: activations stay in the decode activation layout between
         kernels, every LayerNorm is folded into the weights of the Linear it feeds (its row statistics are published by the GEMM that produced
         its input) or applied to the residual operand in an epilogue, the LM head's transform LayerNorm included: 8 launches per layer + 2.
-        x0: embedding output (already LayerNorm'ed + dropped) in the decode activation layout. Returns fp32 logits [B, V]."""
+        x0: embedding output (already LayerNorm'ed + dropped) in the decode activation layout. Returns fp32 logits [B, V].
+        extra (StepRecord): after each attention launch ops.attention_decode_probs on the same q, K view, mask and dropout tuple, and the hidden
+        states by ops.dec_hidden_record after the embedding and after each layer's ffn2. The step's own launches do not change: where the query
+        projection runs inside the cross-attention kernel that launch stays, and q2 for the record comes from one extra dec_gemm of the packed cq."""
         cfg, st, p = self.cfg, self.s, self.p
         D, F, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
         nh, eps, scale = cfg.num_attention_heads, cfg.layer_norm_eps, cfg.head_dim ** -0.5
@@ -853,6 +929,18 @@ class BertEngine:
             return dict(residual=cur, stats=cur_st, rgb=pk[("rgb", cur_ln)], eps=eps) if cur_ln is not None else dict(residual=cur)
 
         lora_kw = dict(lora=(float(cfg.lora_dropout), seed, cfg.lora_alpha / cfg.lora_r, past)) if lora_tr else {}
+        want_attn, want_hidden = extra is not None and extra.attn, extra is not None and extra.hidden_on
+        if want_hidden:
+            extra.hidden_dal(0, x0, B)
+
+        def cross_probs(q2):
+            bits = cache.enc_bits if enc_mask is not None else None
+            extra.decode_probs("cross", l, q2, cache.ck[l], nh, scale, kpm=enc_mask if bits is None else None, kpm_bits=bits,
+                               drop=(pa, seed, _site(l, 2), past))
+
+        def layer_hidden():
+            extra.hidden_dal(l + 1, cur, B, st.f32(cur_ln + ".weight"), st.f32(cur_ln + ".bias"), eps)
+
         for l in range(cfg.num_hidden_layers):
             lp = p + f"bert.encoder.layer.{l}."
             q = torch.empty((B, D), dtype=BF16, device=dev)
@@ -867,6 +955,8 @@ class BertEngine:
             # workgroups + a merge launch (4.8 us per layer; the looping pass costs ~2)
             ctx = ops.attention_decode(q, cache.k[l][:, :past + 1, :], cache.v[l][:, :past + 1, :], nh, scale, kpm=attn_mask_full,
                                        drop=(pa, seed, _site(l, 0), past), wg_keys=256 if past + 1 <= 256 else -256, out_dal=True)
+            if want_attn:
+                extra.decode_probs("self", l, q, cache.k[l][:, :past + 1, :], nh, scale, kpm=attn_mask_full, drop=(pa, seed, _site(l, 0), past))
             (a1,), st1 = ops.dec_gemm(ctx, B, D, [prob((l, "attn_out"), D)], out_stats=True, drop=drop(_site(l, 1)), **res_kw())
             cur, cur_st, cur_ln = a1, st1, lp + "attention.output.LayerNorm"
             Bkv, Tk = cache.ck[l].shape[0], cache.ck[l].shape[1]
@@ -876,11 +966,17 @@ class BertEngine:
                 wp, bc = pk[(l, "cq")]
                 ctx2 = ops.attention_cross_mfma_q(cur, B, cur_st, eps, wp, bc, cache.cpk[l], Bkv, Tk, nh, scale,
                                                   kpm_bits=cache.enc_bits if enc_mask is not None else None, drop=(pa, seed, _site(l, 2), past), out_dal=True)
+                if want_attn:                                  # the same projection as a launch of its own, for the record only
+                    q2 = torch.empty((B, D), dtype=BF16, device=dev)
+                    ops.dec_gemm(cur, B, D, [prob((l, "cq"), D, q2)], stats=cur_st, eps=eps)
+                    cross_probs(q2)
                 (a2,), st2 = ops.dec_gemm(ctx2, B, D, [prob((l, "cout"), D)], out_stats=True, drop=drop(_site(l, 3)), **res_kw())
                 cur, cur_st, cur_ln = a2, st2, lp + "crossattention.output.LayerNorm"
                 (f,), _ = ops.dec_gemm(cur, B, D, [prob((l, "ffn1"), F)], act=1, stats=cur_st, eps=eps)
                 (a3,), st3 = ops.dec_gemm(f, B, F, [prob((l, "ffn2"), D)], out_stats=True, drop=drop(_site(l, 4)), **res_kw())
                 cur, cur_st, cur_ln = a3, st3, lp + "output.LayerNorm"
+                if want_hidden:
+                    layer_hidden()
                 continue
             q2 = torch.empty((B, D), dtype=BF16, device=dev)
             ops.dec_gemm(cur, B, D, [prob((l, "cq"), D, q2)], stats=cur_st, eps=eps)
@@ -891,11 +987,15 @@ class BertEngine:
             else:
                 ctx2 = ops.attention_decode(q2, cache.ck[l], cache.cv[l], nh, scale, kpm=enc_mask, drop=(pa, seed, _site(l, 2), past),
                                             wg_keys=_CROSS_WG_KEYS, out_dal=True, kpm_bits=cache.enc_bits if enc_mask is not None else None)
+            if want_attn:
+                cross_probs(q2)
             (a2,), st2 = ops.dec_gemm(ctx2, B, D, [prob((l, "cout"), D)], out_stats=True, drop=drop(_site(l, 3)), **res_kw())
             cur, cur_st, cur_ln = a2, st2, lp + "crossattention.output.LayerNorm"
             (f,), _ = ops.dec_gemm(cur, B, D, [prob((l, "ffn1"), F)], act=1, stats=cur_st, eps=eps)
             (a3,), st3 = ops.dec_gemm(f, B, F, [prob((l, "ffn2"), D)], out_stats=True, drop=drop(_site(l, 4)), **res_kw())
             cur, cur_st, cur_ln = a3, st3, lp + "output.LayerNorm"
+            if want_hidden:
+                layer_hidden()
         cache.len = past + 1
         wp, bc = pk["transform"]
         (t,), stt = ops.dec_gemm(cur, B, D, [dict(wp=wp, bc=bc, N=D, fold=True)], act=1, stats=cur_st, eps=eps, out_stats=True)

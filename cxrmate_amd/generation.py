@@ -34,7 +34,8 @@ GENERATION_DEFAULTS = dict(
     max_length=None, max_new_tokens=None, bos_token_id=None, eos_token_id=None, pad_token_id=None, num_beams=1, do_sample=False, top_k=50, top_p=1.0,
     temperature=1.0, output_scores=False, return_dict_in_generate=False, use_cache=True, length_penalty=1.0, repetition_penalty=1.0,
     no_repeat_ngram_size=0, min_length=0, min_new_tokens=None, num_return_sequences=1, output_logits=False, bad_words_ids=None, suppress_tokens=None,
-    begin_suppress_tokens=None, sequence_bias=None, forced_bos_token_id=None, forced_eos_token_id=None, early_stopping=False)
+    begin_suppress_tokens=None, sequence_bias=None, forced_bos_token_id=None, forced_eos_token_id=None, early_stopping=False,
+    output_attentions=False, output_hidden_states=False)
 
 # fields of a `generation_config` object this engine cannot honour -> is the value neutral (the field then changes nothing in the library either)?
 _UNSUPPORTED_FIELDS = {
@@ -168,18 +169,30 @@ class Controls(NamedTuple):
 
 
 RECORDED = ("scores", "logits")                                # the per-step outputs, in the order TF5's generate outputs list them
+MAP_FIELDS = ("decoder_attentions", "cross_attentions", "decoder_hidden_states")      # ... and the per-step, per-layer ones that follow them
 
 
 class Record(NamedTuple):
-    """The per-step outputs a call asks for (output_logits / output_scores): which of the two, and the number of row groups of the study-major
-    permutation they are stored under (decode row g * (rows // row_groups) + study -> output row study * row_groups + g)."""
+    """The per-step outputs a call asks for (output_logits / output_scores, output_attentions / output_hidden_states): which of them, and the
+    number of row groups of the study-major permutation they are stored under (decode row g * (rows // row_groups) + study -> output row
+    study * row_groups + g)."""
     logits: bool = False
     scores: bool = False
     row_groups: int = 1
+    attentions: bool = False
+    hidden: bool = False
 
     @property
     def on(self):
         return self.logits or self.scores
+
+    @property
+    def maps(self):                                          # attention maps / hidden states: extra launches inside the decoder step
+        return self.attentions or self.hidden
+
+    @property
+    def any(self):
+        return self.on or self.maps
 
 
 def _plain(v):
@@ -316,6 +329,8 @@ class DecodeSession:
         self.fills = 0                                     # number of reset()s = prefills: every one overwrites the cross K / V (decoder.SharedCrossKV)
         self.beam = None                                   # device-side beam-search state (beam_state)
         self.rec_bufs = {}                                 # per-step outputs of generate (output_logits / output_scores): [Lmax, rows, V] fp32 each
+        self.map_bufs = {}                                 # ... (output_attentions / output_hidden_states): map_buffers
+        self.first_maps = None                             # the prefill step's maps / states (fresh tensors: their q_len is the fed prompt's)
         self.cons = {}                                     # token constraints (hashable description) -> their device tables (constraint_tables)
         self._cache_home = (list(self.cache.k), list(self.cache.v), list(self.cache.k2), list(self.cache.v2))
 
@@ -369,9 +384,49 @@ class DecodeSession:
                 self.rec_bufs[name] = torch.empty((self.Lmax, self.ids.shape[0], V), dtype=torch.float32, device=self.ids.device)
         return {name: self.rec_bufs[name] for name in RECORDED if getattr(record, name)}
 
+    def map_buffers(self, record):
+        """Static slots of the attention maps / hidden states of the single-token steps, step column c -> slot c: "self" fp32
+        [Lmax, L, rows, H, Lmax], "cross" [Lmax, L, rows, H, S] (output_attentions), "hidden" [Lmax, L + 1, rows, D] (output_hidden_states).
+        Like record_buffers: allocated on the first call that asks, never replaced, untouched by calls that do not ask. Bytes:
+        4 * Lmax * rows * (L * H * (Lmax + S) + (L + 1) * D)."""
+        cfg, rows, dev = self.model.config.decoder, self.ids.shape[0], self.ids.device
+        L, H, D = cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size
+        if record.attentions and "self" not in self.map_bufs:
+            self.map_bufs["self"] = torch.zeros((self.Lmax, L, rows, H, self.Lmax), dtype=torch.float32, device=dev)
+            self.map_bufs["cross"] = torch.zeros((self.Lmax, L, rows, H, self.S), dtype=torch.float32, device=dev)
+        if record.hidden and "hidden" not in self.map_bufs:
+            self.map_bufs["hidden"] = torch.zeros((self.Lmax, L + 1, rows, D), dtype=torch.float32, device=dev)
+        return {name: self.map_bufs[name] for name in (("self", "cross") if record.attentions else ()) + (("hidden",) if record.hidden else ())}
+
+    def step_record(self, record, cur, prefill):
+        """The decoder.StepRecord of step column `cur`: its slots, or (prefill) fresh tensors, kept in first_maps. None without the flags."""
+        if not record.maps:
+            return None
+        from .decoder import StepRecord
+        if prefill:
+            self.first_maps = StepRecord(record.attentions, record.hidden, row_groups=record.row_groups)
+            return self.first_maps
+        b = self.map_buffers(record)
+        return StepRecord(record.attentions, record.hidden, b["self"][cur] if "self" in b else None, b["cross"][cur] if "cross" in b else None,
+                          b["hidden"][cur] if "hidden" in b else None, record.row_groups)
+
     def records(self, record, first, steps):
-        """One copy of the recorded outputs of steps first .. first+steps-1 (the session is reused by the next call): name -> tuple of [rows, V]."""
-        return {name: buf[first:first + steps].clone().unbind(0) for name, buf in self.record_buffers(record).items()}
+        """One copy of the recorded outputs of steps first .. first+steps-1 (the session is reused by the next call): name -> tuple of [rows, V];
+        with output_attentions / output_hidden_states also the MAP_FIELDS: per step a tuple over layers, step 0 the prefill's fresh tensors
+        ([rows, H, Tp, Tp] / [rows, H, Tp, S] / [rows, Tp, D]), step t [rows, H, 1, Tp + t] / [rows, H, 1, S] / [rows, 1, D]."""
+        out = {name: buf[first:first + steps].clone().unbind(0) for name, buf in self.record_buffers(record).items()}
+        if record.maps:
+            fm, b = self.first_maps, self.map_buffers(record)
+            self.first_maps = None
+            cp = {name: buf[first + 1:first + steps].clone() for name, buf in b.items()}      # [steps - 1, L (+ 1), rows, ...]
+            if record.attentions:
+                Tp = fm.self_attn[0].shape[3]
+                out["decoder_attentions"] = (tuple(fm.self_attn),) + tuple(tuple(m[:, :, :Tp + t + 1].unsqueeze(2) for m in st.unbind(0))
+                                                                           for t, st in enumerate(cp["self"].unbind(0)))
+                out["cross_attentions"] = (tuple(fm.cross_attn),) + tuple(tuple(m.unsqueeze(2) for m in st.unbind(0)) for st in cp["cross"].unbind(0))
+            if record.hidden:
+                out["decoder_hidden_states"] = (tuple(fm.hidden),) + tuple(tuple(h.unsqueeze(1) for h in st.unbind(0)) for st in cp["hidden"].unbind(0))
+        return out
 
     def _swap_caches(self, n=1):
         c = self.cache
@@ -404,6 +459,7 @@ class DecodeSession:
         self.polled = None
         # what the steps of `plan` bake the address of, made before the first of them is captured (never from inside a capture)
         self.record_buffers(plan.record)
+        self.map_buffers(plan.record)
         if plan.controls.constrained:
             self.constraint_tables(plan.controls.cons)
 
@@ -462,6 +518,7 @@ class DecodeSession:
         slots = self.record_buffers(plan.record)
         lo, so = (slots[name][cur] if name in slots else None for name in ("logits", "scores"))
         tables = self.cons[plan.controls.cons] if plan.controls.constrained else None
+        extra = self.step_record(plan.record, cur, prefill)       # attention maps / hidden states: launches beside the step's own
         if prefill:
             fed = self.ids[:, strip:cur]
             new, mask, tt, pos = m._step_inputs(fed, special, plan.mask_token_id, prefill=True)
@@ -479,21 +536,21 @@ class DecodeSession:
                 # ... and the embeddings of the new token in the same launch, written in the decode kernels' activation layout
                 ph, _, _ = m._dec._dropout_cfg(train, self.seed)
                 x0 = ops.decode_step_embed(*step_args, *m._dec.embed_tables(), drop=(ph, self.seed, 1) if ph else None)
-                logits = m._dec.decode_embedded(self.cache, x0, self.B, self.enc_mask8, mask, train=train, seed=self.seed)
+                logits = m._dec.decode_embedded(self.cache, x0, self.B, self.enc_mask8, mask, train=train, seed=self.seed, extra=extra)
                 new = None
             else:
                 ops.decode_step_inputs(*step_args)
                 new, tt = self.new_id, self.tt1
                 pos = self.pos1 if longi else None
         if new is not None:
-            logits = m._dec.decode(self.cache, new, self.enc16, self.enc_mask8, mask, tt, pos, train=train, seed=self.seed)
+            logits = m._dec.decode(self.cache, new, self.enc16, self.enc_mask8, mask, tt, pos, train=train, seed=self.seed, extra=extra)
         score_step_(logits, self.ids, cur, plan, lo, so, tables)
         if plan.kind == "beam":                                     # one launch: scoring, candidate search, bookkeeping; one more: cache reorder
             nb, es, st, c = plan.num_beams, plan.early_stopping, self.beam, self.cache
             ops.beam_step(logits, self.ids.view(nb, self.B // nb, self.Lmax), st["sequences"], st["run_scores"], st["beam_scores"], st["finished"],
                           st["unsat"], st["allhit"], st["beam_idx"], cur, plan.max_length, eos,
                           float(cur + 1 - plan.prompt_len) ** plan.length_penalty, ws=st["ws"], logprobs=plan.controls.active,
-                          bidx=(st["run_bidx"], st["fin_bidx"]) if plan.record.on else None,
+                          bidx=(st["run_bidx"], st["fin_bidx"]) if plan.record.any else None,
                           early=None if not es else (es, float(plan.max_length - plan.prompt_len) ** plan.length_penalty if es == 2 else 0.0,
                                                      st.get("allfin")))
             ops.gather_batch_multi(c.k + c.v, st["beam_idx"], c.len, c.k2 + c.v2)
@@ -558,11 +615,13 @@ class GenerationMixin:
                   forced_tokens=None, record_inputs=False, repetition_penalty=UNSET, no_repeat_ngram_size=UNSET, min_length=UNSET,
                   min_new_tokens=UNSET, num_return_sequences=UNSET, output_logits=UNSET, bad_words_ids=UNSET, suppress_tokens=UNSET,
                   begin_suppress_tokens=UNSET, sequence_bias=UNSET, forced_bos_token_id=UNSET, forced_eos_token_id=UNSET, early_stopping=UNSET,
-                  generation_config=None, **unused):
+                  output_attentions=UNSET, output_hidden_states=UNSET, generation_config=None, **unused):
         """Options left at UNSET take the non-None field of `generation_config` (any object with attributes), else the engine's default
         (GENERATION_DEFAULTS, resolve_generation_options). Token constraints (bad_words_ids, suppress_tokens, begin_suppress_tokens, sequence_bias,
         forced_bos_token_id, forced_eos_token_id) follow transformers 5.15.0's processors, in its order, in one launch per step
-        (csrc/logits_proc.hip); early_stopping is False, True or "never" (beam search)."""
+        (csrc/logits_proc.hip); early_stopping is False, True or "never" (beam search). output_attentions / output_hidden_states (with
+        return_dict_in_generate): decoder_attentions, cross_attentions / decoder_hidden_states of every step (MAP_FIELDS), fp32, study-major;
+        the encoder returns neither, so encoder_attentions / encoder_hidden_states read None."""
         from .modelling import ModelOutput
         args = locals()
         o = resolve_generation_options({k: args[k] for k in GENERATION_DEFAULTS}, generation_config)
@@ -627,6 +686,8 @@ class GenerationMixin:
         # per-step outputs (TF5 GenerateOutput fields): recorded only when the dict output asks for them
         want_logits = bool(o["output_logits"]) and bool(return_dict_in_generate)
         want_scores = bool(output_scores) and bool(return_dict_in_generate)
+        want_attn = bool(o["output_attentions"]) and bool(return_dict_in_generate)
+        want_hidden = bool(o["output_hidden_states"]) and bool(return_dict_in_generate)
         common = dict(special=tuple(special_token_ids), mask_token_id=mask_token_id, bos=bos_token_id, eos=eos_token_id, max_length=int(max_length),
                       train=bool(self.training), controls=controls)
         rec_out = {}
@@ -637,21 +698,22 @@ class GenerationMixin:
             on_device = self.device_beam_search and num_beams in (2, 4) and 2 * self.config.decoder.num_hidden_layers <= 16
             # (the device search decodes beam-major rows, stored study-major over num_beams row groups; the host loop's rows are study-major already)
             plan = StepPlan(kind="beam", **common, pad=0 if pad_token_id is None else pad_token_id,
-                            record=Record(want_logits, want_scores, num_beams if on_device else 1), num_beams=num_beams,
+                            record=Record(want_logits, want_scores, num_beams if on_device else 1, want_attn, want_hidden), num_beams=num_beams,
                             length_penalty=float(o["length_penalty"]), prompt_len=prompt_len, early_stopping=es)
             with torch.no_grad():
                 seqs, seq_scores = (self._beam_search_session if on_device else self._beam_search)(ids, enc16, enc_mask8, plan, n_ret, rec_out)
             if return_dict_in_generate:         # TF5 GenerateBeamEncoderDecoderOutput field order: rec_out holds scores, logits, beam_indices
-                return ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None, **rec_out)
+                maps = {k: rec_out.pop(k) for k in MAP_FIELDS if k in rec_out}                # ... and the maps / states, which follow them
+                return ModelOutput(sequences=seqs, sequences_scores=seq_scores if output_scores else None, **rec_out, **maps)
             return seqs
 
         rec, keep_inputs = {"tt": [], "pos": []}, (output_scores and do_sample) or record_inputs
         margins = []
         # greedy scores and every call's logits are recorded per step: never served by / decoded along the SCST speculative greedy pass
-        record = Record(want_logits, want_scores and not do_sample, n_ret)
+        record = Record(want_logits, want_scores and not do_sample, n_ret, want_attn, want_hidden)
         warpers = dict(top_k=int(top_k or 0), temperature=float(temperature), top_p=top_p) if do_sample else {}
         plan = StepPlan(kind="sample" if do_sample else "greedy", **common, pad=pad_token_id, record=record, **warpers)
-        plain = forced_tokens is None and not return_margins and not record_inputs and not controls.active and n_ret == 1 and not record.on
+        plain = forced_tokens is None and not return_margins and not record_inputs and not controls.active and n_ret == 1 and not record.any
         if n_ret > 1:
             # sampling of n sequences per study: B * n rows, sample-major (row j * B + b) over ONE copy of the encoder rows when the decode
             # kernels can share them (2 or 4 query rows per K/V stream), else over repeated rows; returned study-major (TF5 repeat_interleave)
@@ -714,6 +776,9 @@ class GenerationMixin:
             if margins:
                 out["greedy_tokens"] = torch.stack([m[0] for m in margins], 1)
                 out["greedy_margins"] = torch.stack([m[1] for m in margins], 1)
+            for k in MAP_FIELDS:                            # TF5 GenerateEncoderDecoderOutput order among themselves, keys only when asked for
+                if k in rec_out:
+                    out[k] = rec_out[k]
             return out
         return ids
 
@@ -727,6 +792,7 @@ class GenerationMixin:
         eos, pad, max_length = plan.eos, plan.pad, plan.max_length
         margins = []
         got = {name: [] for name in RECORDED if getattr(plan.record, name)}
+        kept = self._kept_maps(plan.record)
         tables = constraint_tables(plan.controls.cons, dev) if plan.controls.constrained else None
         with torch.no_grad():
             cache = self._dec.new_cache(B, max_length, dev)
@@ -740,8 +806,10 @@ class GenerationMixin:
                     rec["tt"].append(tt.clone())
                     rec["pos"].append(None if pos is None else pos.clone())
                     rec["seed"] = seed
+                extra = self._step_record_kept(plan.record)
                 logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
-                                          seed=seed)
+                                          seed=seed, extra=extra)
+                self._keep_maps(kept, extra)
                 self._score_step_kept(logits, ids, ids.shape[1], plan, tables, got)      # the whole running history (BOS, prompt, generated)
                 if forced_tokens is not None:
                     greedy_tok, mg = ops.select_token(logits, need_margin=True)
@@ -760,8 +828,27 @@ class GenerationMixin:
                     break
                 if eos is not None and forced_tokens is None and int(unfinished.max()) == 0:
                     break
-        rec_out.update({name: tuple(kept) for name, kept in got.items()})
+        rec_out.update({name: tuple(k_) for name, k_ in got.items()})
+        rec_out.update({name: tuple(k_) for name, k_ in kept.items()})
         return ids, margins
+
+    # the maps / states of a loop without static buffers (_generate_eager, _beam_search): every step's StepRecord returns fresh tensors
+    @staticmethod
+    def _kept_maps(record):
+        return {name: [] for name in ((MAP_FIELDS[:2] if record.attentions else ()) + (MAP_FIELDS[2:] if record.hidden else ()))}
+
+    @staticmethod
+    def _step_record_kept(record):
+        if not record.maps:
+            return None
+        from .decoder import StepRecord
+        return StepRecord(record.attentions, record.hidden, row_groups=record.row_groups)
+
+    @staticmethod
+    def _keep_maps(kept, extra):
+        for name, got in (("decoder_attentions", "self_attn"), ("cross_attentions", "cross_attn"), ("decoder_hidden_states", "hidden")):
+            if name in kept:
+                kept[name].append(tuple(getattr(extra, got)))
 
     @staticmethod
     def _score_step_kept(logits, ids, cur, plan, tables, got):
@@ -952,7 +1039,7 @@ class GenerationMixin:
             ses = self._session(B * nb, enc16.shape[1], max_length, enc_mask8 is not None, share=nb)
             ses.reset(ids.repeat(nb, 1), enc16, enc_mask8, plan)
             ses.ids[:, prompt_len:] = plan.pad
-            st = ses.beam_state(nb, plan.pad, bidx=plan.record.on, allfin=es == 1)
+            st = ses.beam_state(nb, plan.pad, bidx=plan.record.any, allfin=es == 1)
 
             def going():                                                # flags of the last executed step (column cur - 1)
                 par = (cur - 1) & 1
@@ -970,7 +1057,7 @@ class GenerationMixin:
             # the finished set is held best first: [n, B] -> study-major rows
             out = st["sequences"][:n_ret].transpose(0, 1).reshape(B * n_ret, st["sequences"].shape[2]).clone()
             scores = st["beam_scores"][:, :n_ret].reshape(-1).clone()
-            if plan.record.on:
+            if plan.record.any:
                 # steps the search ran (later launches are frozen): every running beam has a parent in each of their columns
                 steps = int((st["run_bidx"][0, 0, prompt_len:] >= 0).sum())
                 rec_out.update(ses.records(plan.record, prompt_len, steps))
@@ -990,7 +1077,7 @@ class GenerationMixin:
         dev = ids.device
         B = ids.shape[0]
         nb, keep = plan.num_beams, 2 * plan.num_beams
-        eos, pad, max_length, es, length_penalty, record = plan.eos, plan.pad, plan.max_length, plan.early_stopping, plan.length_penalty, plan.record.on
+        eos, pad, max_length, es, length_penalty, record = plan.eos, plan.pad, plan.max_length, plan.early_stopping, plan.length_penalty, plan.record.any
         V = self.config.decoder.vocab_size
         ids = ids.repeat_interleave(nb, dim=0)
         enc16 = enc16.repeat_interleave(nb, dim=0).contiguous()
@@ -1010,6 +1097,7 @@ class GenerationMixin:
         seed = self.next_dropout_seed() if self.training else None
         tables = constraint_tables(plan.controls.cons, dev) if plan.controls.constrained else None
         got = {name: [] for name in RECORDED if getattr(plan.record, name)}
+        kept = self._kept_maps(plan.record)
         if record:                                                 # beam-index histories (TF5:gen:3348-3351), absolute token columns
             run_bidx = torch.full((B, nb, max_length), -1, dtype=torch.int32, device=dev)
             fin_bidx = run_bidx.clone()
@@ -1023,8 +1111,10 @@ class GenerationMixin:
             flat = running[:, :, :cur].reshape(B * nb, cur)
             fed = self._fed(flat, plan.bos)
             new, mask, tt, pos = self._step_inputs(fed, plan.special, plan.mask_token_id, prefill=cache.len == 0)
+            extra = self._step_record_kept(plan.record)
             logits = self._dec.decode(cache, new.contiguous(), enc16, enc_mask8, mask, tt.contiguous(), None if pos is None else pos.contiguous(),
-                                      seed=seed)
+                                      seed=seed, extra=extra)
+            self._keep_maps(kept, extra)
             self._score_step_kept(logits, flat.contiguous(), cur, plan, tables, got)
             if plan.controls.active:                                                          # processed log-probs (TF5:gen:3388-3389) + running beam score
                 logits.add_(run_scores.view(-1, 1))
@@ -1065,6 +1155,7 @@ class GenerationMixin:
         out = sequences[:, 0, :] if n_ret == 1 else sequences[:, :n_ret, :].reshape(B * n_ret, -1)
         sc = beam_scores[:, 0] if n_ret == 1 else beam_scores[:, :n_ret].reshape(-1)
         if record:
-            rec_out.update({name: tuple(kept) for name, kept in got.items()})
+            rec_out.update({name: tuple(k_) for name, k_ in got.items()})
+            rec_out.update({name: tuple(k_) for name, k_ in kept.items()})
             rec_out["beam_indices"] = self._trim_beam_indices(fin_bidx[:, :n_ret, prompt_len:].reshape(B * n_ret, -1))
         return trim_at_eos(out, prompt_len, eos), sc

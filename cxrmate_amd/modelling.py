@@ -33,7 +33,7 @@ class ModelOutput(dict):
     """Minimal stand-in for transformers' ModelOutput: attribute, key and integer access; item assignment
     (the SCST caller does `sample['sequences'] = ...`, reference scst/gt_prompt.py:185-186). The optional Seq2SeqLMOutput fields below are
     keys only when they were asked for (output_attentions / output_hidden_states), as in transformers; as attributes they read None otherwise."""
-    _OPTIONAL = ("decoder_hidden_states", "decoder_attentions", "cross_attentions")
+    _OPTIONAL = ("decoder_hidden_states", "decoder_attentions", "cross_attentions", "encoder_attentions", "encoder_hidden_states")
 
     def __getattr__(self, k):
         try:
@@ -603,7 +603,7 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
             raise ValueError("You have to specify exactly one of decoder_input_ids or decoder_inputs_embeds")
         if past_key_values is not None:
             return self._forward_cached(decoder_input_ids, enc, enc_mask, decoder_attention_mask, kwargs_decoder, past_key_values, labels,
-                                        decoder_inputs_embeds, return_dict)
+                                        decoder_inputs_embeds, return_dict, output_attentions, output_hidden_states)
         collect = {k for k, on in (("attn", output_attentions), ("hidden", output_hidden_states)) if on} or None
         logits = self._decode_tf(decoder_input_ids, enc, enc_mask, decoder_attention_mask, kwargs_decoder.get("token_type_ids"),
                                  kwargs_decoder.get("position_ids"), embeds=decoder_inputs_embeds, collect=collect)
@@ -635,12 +635,14 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
             return out.to_tuple()
         return out
 
-    def _forward_cached(self, ids, enc, enc_mask, attn_mask, kwargs_decoder, past, labels, embeds, return_dict):
+    def _forward_cached(self, ids, enc, enc_mask, attn_mask, kwargs_decoder, past, labels, embeds, return_dict, output_attentions=None,
+                        output_hidden_states=None):
         """forward(..., past_key_values=cache) for callers that run their own decoding loop (transformers' generate does exactly this through
         prepare_inputs_for_generation, modelling_longitudinal.py:251-295): `past_key_values` is the engine's own KV cache object (opaque: hand back what the
         previous call returned), decoder_input_ids holds the NEW token of every row, decoder_attention_mask the full mask [B, past + new]. Gradient-free
         (the cached kernels have no backward). Logits come back for the fed position, [B, 1, V], as from the library; feeding several new tokens on top
-        of a non-empty cache (chunked prefill) is not something the reference's callers do and is refused rather than answered with one position."""
+        of a non-empty cache (chunked prefill) is not something the reference's callers do and is refused rather than answered with one position.
+        output_attentions / output_hidden_states: the maps and states of the FED positions (decoder.StepRecord), fields as on the teacher-forced path."""
         if labels is not None or embeds is not None:
             raise NotImplementedError("past_key_values: decoder_input_ids only, no labels (the cached path is the decoding path)")
         if torch.is_grad_enabled() and any(p.requires_grad for _, p in self._grad_params("decoder.")):
@@ -657,9 +659,17 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         if cache.len + Tn > cache.Tmax:
             raise ValueError(f"cache holds {cache.len} positions, {Tn} more exceed max_position_embeddings = {cache.Tmax}")
         seed = self.next_dropout_seed() if self.training else None
+        from .decoder import StepRecord
+        extra = StepRecord(output_attentions, output_hidden_states) if (output_attentions or output_hidden_states) else None
         logits = self._dec.decode(cache, ids, enc16, self._u8(enc_mask, dev), self._u8(attn_mask, dev), self._i64(kwargs_decoder.get("token_type_ids"), dev),
-                                  self._i64(kwargs_decoder.get("position_ids"), dev), train=self.training, seed=seed)
-        out = ModelOutput(loss=None, logits=logits.view(B, 1, -1), past_key_values=cache, encoder_last_hidden_state=enc)
+                                  self._i64(kwargs_decoder.get("position_ids"), dev), train=self.training, seed=seed, extra=extra)
+        out = ModelOutput(loss=None, logits=logits.view(B, 1, -1), past_key_values=cache)
+        if output_hidden_states:
+            out["decoder_hidden_states"] = tuple(extra.hidden)
+        if output_attentions:
+            out["decoder_attentions"] = tuple(extra.self_attn)
+            out["cross_attentions"] = tuple(extra.cross_attn)
+        out["encoder_last_hidden_state"] = enc
         return out.to_tuple() if return_dict is False else out
 
     @staticmethod

@@ -1427,6 +1427,44 @@ def attention_decode(q, k, v, heads, scale, kpm=None, out=None, drop=None, head_
     return out
 
 
+def attention_decode_probs(q, k, heads, scale, kpm=None, kpm_bits=None, drop=None, out=None, row_groups=1):
+    """The probabilities behind a single-query attention of a cached step (attention_decode / attention_cross_mfma / attention_cross_mfma_q on the same
+    q, K view, mask and dropout tuple) -> fp32 [B, H, 1, Tk] (csrc/attn_decode_probs.hip). q [B,1,H*64] or [B,H*64]; k [B / share, Tk, H*64] view
+    (share 1, 2, 4; batch / row strides free); kpm uint8 [B / share, Tk] or kpm_bits (pack_mask_bits). out: fp32 [B, H, Tk] or [B, H, 1, Tk] with any
+    strides (a slot of a larger buffer); decode row g * (B // row_groups) + s is written to out row s * row_groups + g."""
+    B = q.shape[0]
+    Bkv, Tk, D = k.shape
+    share = B // Bkv
+    assert Bkv * share == B and share in (1, 2, 4) and D == heads * 64 and q.shape[-1] == D and B % row_groups == 0
+    assert q.dtype == BF16 and k.dtype == BF16 and q.stride(-1) == 1 and k.stride(2) == 1
+    if out is None:
+        out = torch.empty((B, heads, 1, Tk), device=q.device, dtype=torch.float32)
+    o3 = out[:, :, 0, :] if out.dim() == 4 else out
+    assert o3.dtype == torch.float32 and o3.shape == (B, heads, Tk)
+    if kpm_bits is not None:                                    # bit words (row stride in bytes), as attention_decode takes them
+        assert kpm_bits.shape[0] == Bkv and kpm_bits.shape[1] * 32 >= Tk
+        mask, mask_bs, bits = kpm_bits, kpm_bits.stride(0) * 4, 1
+    else:
+        assert kpm is None or (kpm.dtype == torch.uint8 and kpm.shape == (Bkv, Tk) and kpm.stride(1) == 1)
+        mask, mask_bs, bits = kpm, (kpm.stride(0) if kpm is not None else 0), 0
+    LIB.call("cxr_attn_decode_probs_f32", _p(q), _p(k), _p(mask), _p(o3), q.stride(0), k.stride(0), k.stride(1), mask_bs, o3.stride(0), o3.stride(1),
+             max(o3.stride(2), 1), B, heads, Tk, float(scale), share, bits, *_drop_args(drop), int(row_groups), _s())
+    return out if out.dim() == 4 else out.unsqueeze(2)
+
+
+def dec_hidden_record(x_dal, M, gamma=None, beta=None, eps=0.0, out=None, row_groups=1):
+    """fp32 hidden state [M, K] of a fused decode step from its rows in the decode activation layout (csrc/attn_decode_probs.hip): the rows widened
+    (gamma is None: the embedding output) or LayerNorm(gamma, beta, eps) of them, statistics computed by the kernel. out: fp32 [M, K] view (row
+    stride free); decode row g * (M // row_groups) + s is written to out row s * row_groups + g."""
+    K = x_dal.shape[1]
+    assert x_dal.dtype == BF16 and (x_dal.is_contiguous() or not x_dal.is_cuda) and x_dal.shape[0] % 16 == 0 and M <= x_dal.shape[0] and M % row_groups == 0
+    if out is None:
+        out = torch.empty((M, K), device=x_dal.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (M, K) and out.stride(1) == 1
+    LIB.call("cxr_dec_hidden_record_f32", _p(x_dal), x_dal.shape[0] // 16, M, K, _p(gamma), _p(beta), float(eps), _p(out), out.stride(0), int(row_groups), _s())
+    return out
+
+
 def pack_cross_kv(k, v, heads, out=None):
     """k, v [Bkv, Tk, H*64] bf16 (equal strides) -> (Kp, Vp): fragment-ordered copies for attention_cross_mfma (one launch, once per decode)."""
     Bkv, Tk, D = k.shape

@@ -346,6 +346,26 @@ int cxr_logits_constrain_f32(float* logits, long ld, const long* ids, long ids_l
  * study, S = R / nb) written to output row study * nb + beam (nb = 1: the same order). One workgroup per row; capturable. */
 int cxr_gen_record_f32(const float* x, long ld, long R, int V, int nb, float* logits_out, float* scores_out, int log_softmax, hipStream_t stream);
 
+/* ---- attention maps and hidden states of a cached decode step (TF5:gen:2906-2921 _sample, :3398-3412 _beam_search: output_attentions /
+ * output_hidden_states collect the step's decoder_attentions / cross_attentions / decoder_hidden_states). Both run BESIDE the step's own kernels
+ * (csrc/attn_decode_probs.hip); capturable: no workspace, no host reads, no synchronisation.
+ * cxr_attn_decode_probs_f32: the softmax (+ dropout) of TF5 eager_attention_forward (TF5:bert:126-131) for one query per row, which
+ * cxr_attn_decode_bf16 / cxr_attn_cross_mfma_bf16 / cxr_attn_cross_mfma_q_bf16 never form: P(r, h, j) = softmax_j(scale * q_r,h . k_j) fp32 at
+ * P + r' * p_bs + h * p_hs + j * p_ks, from Q bf16 [B, H*64] (row stride q_bs) and K bf16 [B / kv_share, Tk, H*64] (strides k_bs, k_rs); query
+ * rows b + g * (B / kv_share) read K row b and mask row b (kv_share 1, 2, 4). kpm: NULL, bytes [*, Tk] (row stride kpm_bs), or with kpm_bits != 0
+ * the bit words of cxr_pack_mask_bits (kpm_bs in BYTES); entries it hides are exactly 0, a row it hides entirely is uniform 1 / Tk. drop_p > 0:
+ * the decode kernels' keep mask of (r * H + h, drop_t, key), kept entries times 1 / (1 - p). r' = (r % S) * row_groups + r / S with
+ * S = B / row_groups (decode row g * S + s -> output row s * row_groups + g, as cxr_gen_record_f32 stores the logits). 1 <= Tk <= 8192.
+ * cxr_dec_hidden_record_f32: the hidden state that TF5 BertEncoder (TF5:bert:374-411) appends per layer, which the fused step keeps only as the
+ * un-normalised input of a LayerNorm folded into the next cxr_dec_gemm: x = M rows of width K (K % 32 == 0) in the decode activation layout of
+ * [16 * x_mt, K]; out fp32 (row stride o_rs, rows permuted as above) <- x widened (gamma == beta == NULL: the embedding output) or
+ * LayerNorm(x; gamma, beta, eps) with the row mean / variance computed here in fp32. */
+int cxr_attn_decode_probs_f32(const void* Q, const void* K, const void* kpm, float* P, long q_bs, long k_bs, long k_rs, long kpm_bs, long p_bs,
+                              long p_hs, long p_ks, int B, int H, int Tk, float scale, int kv_share, int kpm_bits, float drop_p,
+                              const unsigned int* drop_seed, unsigned int drop_site, int drop_t, int row_groups, hipStream_t stream);
+int cxr_dec_hidden_record_f32(const void* x, int x_mt, int M, int K, const float* gamma, const float* beta, float eps, float* out, long o_rs,
+                              int row_groups, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3fn) linear layers of the frozen encoder (BASELINE.json configs[4]; caller REF:modules/lightning_modules/longitudinal/scst/
  * gen_prompt.py:174-259, encoder under no_grad). C[M,N] = epi(scale * A8[M,K] . W8[N,K]^T): one scale per tensor (scale = s_A * s_W), fp32
  * accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales; epi = + bias, GELU (act 1), + residual (bf16); output bf16 (C) and / or
