@@ -273,8 +273,8 @@ __global__ __launch_bounds__(DW3_THREADS, 2) void dw3_apply_kernel(const Dw3Geo 
 // when the caller hands over the projection's forward output yf = (c - mean) * gamma * rstd + beta (bf16, saved for the weight gradient of the Linear layer
 // that follows) and, for all 64 channels of the slice, |gamma * rstd| >= 1e-3 and |beta| <= 8 |gamma| -- recovered as c = mean + (yf - beta) / (gamma * rstd):
 // the pass is then a plain streaming reduction over (dy, yf) without the LDS tile, the 9 window reads and the 108 VALU instructions of the convolution
-// per 8 outputs. The bf16 rounding of yf is 2^-9 |yf| (of the whole stored value, beta included), so the normalised activation xhat = (yf - beta) / gamma
-// is recovered with an error of up to 2^-9 (|xhat| + |beta| / |gamma|): the second gate bounds that amplification (<= 2^-9 * (|xhat| + 8): the size of the
+// per 8 outputs. The bf16 rounding of yf is up to 2^-8 |yf| (half a step at the bottom of a binade; of the whole stored value, beta included), so the normalised
+// activation xhat = (yf - beta) / gamma is recovered with an error of up to 2^-8 (|xhat| + |beta| / |gamma|): the second gate bounds that amplification (<= 2^-8 * (|xhat| + 8): the size of the
 // bf16 rounding the activations carry anyway); a slice with a larger |beta| / |gamma| (pretrained BatchNorm parameters can have one) recomputes the
 // convolution. The remaining per-element error is unbiased and averages out in the two sums (tests: same tolerances as the recomputed path).
 __global__ __launch_bounds__(DW3_THREADS, 2) void dw3_bwd_stats_kernel(const Dw3Geo g, const Dw3P p0, const Dw3P p1, const Dw3P p2, float* __restrict__ ws) {
