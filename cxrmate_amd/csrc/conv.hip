@@ -321,6 +321,109 @@ extern "C" int cxr_col2im_tok_bf16(const void* dcol, void* dx, long dx_bs, long 
     return CXR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- stage-1 patch embedding, data gradient
+// dpx[b,c,y,x] = sum_{co} sum_{(oy,ky): oy*stride - pad + ky = y} sum_{(ox,kx): ox*stride - pad + kx = x} de[b,oy,ox,co] * w[co,c,ky,kx]: what autograd's
+// conv2d backward gives for the input of nn.Conv2d(3, Co, ks, stride, pad) (TF5 modeling_cvt.py:77-90), on the bf16 operands the forward multiplied.
+// Gather form: a pixel draws from at most ceil(ks / stride)^2 output positions x Co channels, every pixel is written exactly once (an exact 0.0
+// where no output position covers it), nothing is accumulated into, and the summation order is fixed -> the same bits on every run.
+//   workgroup  = tiles of DG_TQY x TQX cells of stride x stride pixels, grid-stride (the weights are staged once per workgroup, not per tile)
+//   LDS        = the weights as [tap = (c, ky, kx)][co] and the de rows of the output positions the tile's pixels draw from (the tile's own cells
+//                plus the halo), both bf16 with co contiguous and rows padded by 16 bytes: the inner loop is 16-byte LDS reads of 8 channels
+//   lanes      = consecutive x of one pixel row: a wave stores whole 256-byte runs of one channel plane
+// Products of two bf16 values are exact in fp32; the sum is fp32 in the fixed order (oy, ox, co).
+constexpr int DG_CIN = 3;                    // channels of the image
+constexpr int DG_TQY = 4;                    // cell rows per tile
+constexpr int DG_LPAD = 8;                   // bf16 elements of padding per LDS row (16 bytes: neighbouring rows start 4 banks apart)
+
+__global__ __launch_bounds__(256) void patch_embed_dgrad_kernel(const bf16_t* __restrict__ de, const bf16_t* __restrict__ w, float* __restrict__ dpx,
+                                                                int Bn, int H, int W, int Co, int ks, int stride, int pad, int Ho, int Wo, int kpad,
+                                                                int TQX, int NOY, int NOX) {
+    extern __shared__ __attribute__((aligned(16))) bf16_t dg_lds[];          // [DG_CIN * ks * ks][Co + DG_LPAD] weights, then [NOY * NOX][Co + DG_LPAD] de rows
+    const int tid = threadIdx.x;
+    const int ld = Co + DG_LPAD, ntap = DG_CIN * ks * ks, kk = ks * ks, c8n = Co / 8;
+    bf16_t* wl = dg_lds;
+    bf16_t* dl = dg_lds + (long)ntap * ld;
+    for (int e = tid; e < Co * ntap; e += 256) {                             // global reads run along the taps of one output channel
+        const int co = e / ntap, t = e - co * ntap;
+        wl[t * ld + co] = w[(long)co * kpad + t];
+    }
+    const int PY = DG_TQY * stride, PX = TQX * stride;
+    const int tiles_y = (H + PY - 1) / PY, tiles_x = (W + PX - 1) / PX;
+    const long ntiles = (long)Bn * tiles_y * tiles_x;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long)tiles_x * tiles_y));
+        const int y0 = ty * PY, x0 = tx * PX;
+        const int y1 = min(y0 + PY, H), x1 = min(x0 + PX, W);                // (exclusive)
+        // output positions the tile's pixels draw from: oy in [ceil((y0 + pad - ks + 1) / stride), floor((y1 - 1 + pad) / stride)] within [0, Ho)
+        const int ty_lo = y0 + pad - (ks - 1), tx_lo = x0 + pad - (ks - 1);
+        const int oy_lo = ty_lo <= 0 ? 0 : (ty_lo + stride - 1) / stride, ox_lo = tx_lo <= 0 ? 0 : (tx_lo + stride - 1) / stride;
+        const int oy_hi = min((y1 - 1 + pad) / stride, Ho - 1), ox_hi = min((x1 - 1 + pad) / stride, Wo - 1);
+        const int noy = oy_hi - oy_lo + 1, nox = ox_hi - ox_lo + 1;          // (<= NOY, NOX; <= 0 when nothing covers the tile)
+        __syncthreads();                                                     // the previous tile's readers are done (first pass: the weights are staged)
+        if (noy > 0 && nox > 0) {
+            for (int e = tid; e < noy * nox * c8n; e += 256) {
+                const int pos = e / c8n, ch = e - pos * c8n;
+                const int r = pos / nox, q = pos - r * nox;
+                const uint4 v = *reinterpret_cast<const uint4*>(de + (((long)b * Ho + oy_lo + r) * Wo + ox_lo + q) * Co + ch * 8);
+                *reinterpret_cast<uint4*>(dl + (r * NOX + q) * ld + ch * 8) = v;
+            }
+        }
+        __syncthreads();
+        const int npx = (y1 - y0) * PX;
+        for (int i = tid; i < npx; i += 256) {
+            const int yr = i / PX, xr = i - yr * PX;
+            const int y = y0 + yr, x = x0 + xr;
+            if (x >= x1) continue;
+            const int ay = y + pad - (ks - 1), ax = x + pad - (ks - 1);
+            const int oya = max(ay <= 0 ? 0 : (ay + stride - 1) / stride, oy_lo), oxa = max(ax <= 0 ? 0 : (ax + stride - 1) / stride, ox_lo);
+            const int oyb = min((y + pad) / stride, oy_hi), oxb = min((x + pad) / stride, ox_hi);
+            float acc[DG_CIN];
+#pragma unroll
+            for (int c = 0; c < DG_CIN; ++c) acc[c] = 0.f;
+            for (int oy = oya; oy <= oyb; ++oy) {
+                const int ky = y + pad - oy * stride;                        // in [0, ks)
+                for (int ox = oxa; ox <= oxb; ++ox) {
+                    const int kx = x + pad - ox * stride;
+                    const bf16_t* dp = dl + ((oy - oy_lo) * NOX + (ox - ox_lo)) * ld;
+                    const bf16_t* wp = wl + (ky * ks + kx) * ld;
+                    for (int c8 = 0; c8 < c8n; ++c8) {
+                        float d[8];
+                        unpack8(*reinterpret_cast<const uint4*>(dp + c8 * 8), d);
+#pragma unroll
+                        for (int c = 0; c < DG_CIN; ++c) {
+                            float f[8];
+                            unpack8(*reinterpret_cast<const uint4*>(wp + c * kk * ld + c8 * 8), f);
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) acc[c] = fmaf(d[j], f[j], acc[c]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < DG_CIN; ++c) dpx[(((long)b * DG_CIN + c) * H + y) * W + x] = acc[c];
+        }
+    }
+}
+
+extern "C" int cxr_patch_embed_dgrad_f32(const void* de, const void* w, float* dpx, int Bn, int Cin, int H, int W, int Co, int ks, int stride, int pad,
+                                         int Ho, int Wo, int kpad, hipStream_t stream) {
+    if (!de || !w || !dpx || Bn <= 0 || Cin != DG_CIN || H <= 0 || W <= 0 || Co <= 0 || (Co % 8) || ks < 1 || stride < 1 || pad < 0) return CXR_ERR_ARG;
+    if (H + 2 * pad < ks || W + 2 * pad < ks || Ho != (H + 2 * pad - ks) / stride + 1 || Wo != (W + 2 * pad - ks) / stride + 1) return CXR_ERR_ARG;
+    if (kpad < Cin * ks * ks || (((size_t)de) % 16)) return CXR_ERR_ARG;
+    const int TQX = stride <= 64 ? 64 / stride : 1;                          // 64 pixels of a row per tile where the stride allows
+    // integers in an interval of length (T * stride - 1 + ks - 1) / stride: at most T + (ks - 2) / stride + 1
+    const int halo = (ks >= 2 ? (ks - 2) / stride : 0) + 1;
+    const int NOY = DG_TQY + halo, NOX = TQX + halo;
+    const size_t lds = ((size_t)Cin * ks * ks + (size_t)NOY * NOX) * (Co + DG_LPAD) * sizeof(bf16_t);
+    if (lds > 64 * 1024) return CXR_ERR_ARG;
+    const long ntiles = (long)Bn * cdiv(H, DG_TQY * stride) * cdiv(W, TQX * stride);
+    const int grid = (int)(ntiles < 1024 ? ntiles : 1024);
+    CXR_LAUNCH(patch_embed_dgrad_kernel, dim3(grid), dim3(256), lds, stream, (const bf16_t*)de, (const bf16_t*)w, dpx, Bn, H, W, Co, ks, stride, pad,
+               Ho, Wo, kpad, TQX, NOY, NOX);
+    CXR_LAUNCH_CHECK();
+    return CXR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- depthwise 3x3 + BN
 // Folded parameters per projection: wf[9][C] = conv_w[c][tap] * bn_scale[c], sh[C] = bn_bias - mean*bn_scale  (fp32)
 // (eval-mode BatchNorm, TF5 modeling_cvt.py:93-110; the batch-statistics variant feeds batch mean/var through the same fold)

@@ -233,7 +233,7 @@ class CvtEncoderEngine:
         if save:
             self._prepare_transposes()
         Bn = px.shape[0]
-        saved = {"Bn": Bn, "stages": [], "train": train} if save else None
+        saved = {"Bn": Bn, "stages": [], "train": train, "px_hw": (int(px.shape[2]), int(px.shape[3]))} if save else None
         self._train = train
         self._saving = bool(save)
         if self.fp8 is not None and self.fp8["version"] != st.shadow_version and not save:
@@ -431,23 +431,32 @@ class CvtEncoderEngine:
         return x3.view(Bn, L, C), lsave
 
     # ------------------------------------------------------------------------------------------ backward
-    def backward(self, saved, dfeats: torch.Tensor, on_stage_done=None):
+    def backward(self, saved, dfeats: torch.Tensor, on_stage_done=None, need_dpx: bool = False, need_wgrad: bool = True):
         """dfeats [Bn*tokens, projection_size] bf16. Parameter gradients are ACCUMULATED into the store's flat gradient buffer.
         on_stage_done(s): called when every gradient launch of stage s (and of the later stages and the projection head) has been issued --
-        data parallelism starts the all-reduce of that stage's parameters while the earlier stages are still in backward."""
+        data parallelism starts the all-reduce of that stage's parameters while the earlier stages are still in backward.
+        need_dpx: the chain is carried one link further, through the stage-1 convolution (TF5 modeling_cvt.py:77-90) -> the gradient of the pixels,
+        [Bn, 3, H, W] fp32 (the reference's pixel_values.grad); otherwise None is returned and nothing is launched for it.
+        need_wgrad=False: the backward of an all-frozen encoder. Only the dX chain runs: no weight-gradient GEMM, no im2col of the pixels, nothing on
+        the weight-gradient stream; the flat gradient buffer is not touched (the scale / shift sums that the BatchNorm backward kernels produce
+        as by-products go to scratch). Every dx is computed by the same launches on the same operands as with need_wgrad=True: the same bits."""
         cfg, st = self.cfg, self.s
-        ops.wgrad_begin()
+        ops.wgrad_begin()                                               # (also without weight gradients: the dX GEMMs pick the kernels they pick beside that stream)
         prep = self.prepare()
         self._prepare_transposes()
         ops.wgrad_wait(self._wt_event)                                  # transposed weights are ready (NOT a join: the decoder's weight-gradient backlog keeps running)
-        st.ensure_grads()
+        if need_wgrad:
+            st.ensure_grads()
+        grad = st.grad if need_wgrad else (lambda key: None)
         Bn = saved["Bn"]
         hp = self.p + "projection_head."
         C = cfg.embed_dim[-1]
-        ops.linear_bwd_weight(dfeats, saved["hn"], st.grad(hp + "projection.weight"))
+        if need_wgrad:
+            ops.linear_bwd_weight(dfeats, saved["hn"], st.grad(hp + "projection.weight"))
         dhn = ops.gemm_nt(dfeats, self._wt(hp + "projection.weight"))
         dx = ops.layernorm_bwd(saved["x_last"].view(-1, C), dhn, st.f32(hp + "layer_norm.weight"), saved["hstats"],
-                               st.grad(hp + "layer_norm.weight"), st.grad(hp + "layer_norm.bias"))
+                               grad(hp + "layer_norm.weight"), grad(hp + "layer_norm.bias"))
+        dpx = None
         dx = dx.view(Bn, -1, C)                                     # grad wrt stage output tokens (no class token)
         for s in reversed(range(len(cfg.depth))):
             sp = self._stage(s)
@@ -463,76 +472,86 @@ class CvtEncoderEngine:
                 # the layer below scales its incoming gradient by ITS second DropPath factor first thing: let this layer's last kernel write it scaled
                 below = ss["layers"][l - 1]["dp"][1] if l > 0 else None
                 dx = self._layer_bwd(dx, ss["layers"][l], s, l, H, W, tok0, prep, prescaled=l + 1 < cfg.depth[s] and ss["layers"][l]["dp"][1] is not None,
-                                     out_scale=below)
+                                     out_scale=below, need_wgrad=need_wgrad)
             if tok0:
-                ops.sum_row0_into(dx, st.grad(sp + "cls_token").view(-1))
+                if need_wgrad:
+                    ops.sum_row0_into(dx, st.grad(sp + "cls_token").view(-1))
                 dsp = torch.empty((Bn, H * W, C), dtype=torch.bfloat16, device=dx.device)
                 ops.copy_rows(dx[:, 1:, :], dsp)
                 dx = dsp
             ep = sp + "embedding.convolution_embeddings."
             de = ops.layernorm_bwd(ss["e"], dx.view(-1, C), st.f32(ep + "normalization.weight"), ss["estats"],
-                                   st.grad(ep + "normalization.weight"), st.grad(ep + "normalization.bias"))
+                                   grad(ep + "normalization.weight"), grad(ep + "normalization.bias"))
             wp = prep[("embed", s)]
-            dwp = torch.zeros(wp.shape, dtype=torch.float32, device=dx.device)
-            col = ss["col"]
-            if col is None:                                   # implicit-GEMM forward: the im2col matrix is built here, on the weight-gradient stream
-                with ops._on_wgrad_stream(ss["xin"]):
-                    if s == 0:
-                        col = ops.im2col_pixels(ss["xin"], cfg.patch_sizes[0], cfg.patch_stride[0], cfg.patch_padding[0], wp.shape[1])[0]
-                    else:
-                        col = ops.im2col_tokens(ss["xin"], ss["Hin"], ss["Win"], cfg.patch_stride[s], cfg.patch_padding[s])[0]
-            gw = st.grad(ep + "projection.weight")
-            if (s == 0 and _TAIL_ON_MAIN and ss.get("col_ev") is not None and ops.WGRAD_STREAM is not None and not ops._WGRAD_SKIP
-                    and not torch.cuda.is_current_stream_capturing()):
-                # The step's LAST weight gradient (64 x 192 x 589824 at the benchmark batch, ~0.15 ms): its operand `de` is the main stream's last
-                # product, and on the weight-gradient stream it queues behind that stream's backlog of the stage-1 layer -- the main stream, which has
-                # nothing left to do, runs it instead, beside that backlog (profiles/r06_step_tail.txt: 0.33 ms of exposed tail per step before)
-                ops.wgrad_flush()
-                torch.cuda.current_stream().wait_event(ss["col_ev"])
-                col.record_stream(torch.cuda.current_stream())
-                ops.gemm_tn(de, col, dwp, dbias=st.grad(ep + "projection.bias"))
-                gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))
-            else:
-                ops.linear_bwd_weight(de, col, dwp, st.grad(ep + "projection.bias"))
-                with ops._on_wgrad_stream(dwp):                  # same stream as the weight-gradient GEMM that fills dwp (ordered after it)
-                    if s == 0:
-                        gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))                       # layout plumbing back to [Co,Ci,kh,kw]
-                    else:
-                        gw.add_(dwp.view(gw.shape[0], gw.shape[2], gw.shape[3], gw.shape[1]).permute(0, 3, 1, 2))
+            if s == 0 and need_dpx:
+                # the last link: de through the 7 x 7 / stride 4 convolution to the image, with the bf16 weights the forward multiplied
+                dpx = ops.patch_embed_dgrad(de, wp, Bn, saved["px_hw"][0], saved["px_hw"][1], cfg.patch_sizes[0], cfg.patch_stride[0], cfg.patch_padding[0])
+            if need_wgrad:
+                dwp = torch.zeros(wp.shape, dtype=torch.float32, device=de.device)
+                col = ss["col"]
+                if col is None:                                   # implicit-GEMM forward: the im2col matrix is built here, on the weight-gradient stream
+                    with ops._on_wgrad_stream(ss["xin"]):
+                        if s == 0:
+                            col = ops.im2col_pixels(ss["xin"], cfg.patch_sizes[0], cfg.patch_stride[0], cfg.patch_padding[0], wp.shape[1])[0]
+                        else:
+                            col = ops.im2col_tokens(ss["xin"], ss["Hin"], ss["Win"], cfg.patch_stride[s], cfg.patch_padding[s])[0]
+                gw = st.grad(ep + "projection.weight")
+                if (s == 0 and _TAIL_ON_MAIN and ss.get("col_ev") is not None and ops.WGRAD_STREAM is not None and not ops._WGRAD_SKIP
+                        and not torch.cuda.is_current_stream_capturing()):
+                    # The step's LAST weight gradient (64 x 192 x 589824 at the benchmark batch, ~0.15 ms): its operand `de` is the main stream's last
+                    # product, and on the weight-gradient stream it queues behind that stream's backlog of the stage-1 layer -- the main stream, which has
+                    # nothing left to do, runs it instead, beside that backlog (profiles/r06_step_tail.txt: 0.33 ms of exposed tail per step before)
+                    ops.wgrad_flush()
+                    torch.cuda.current_stream().wait_event(ss["col_ev"])
+                    col.record_stream(torch.cuda.current_stream())
+                    ops.gemm_tn(de, col, dwp, dbias=st.grad(ep + "projection.bias"))
+                    gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))
+                else:
+                    ops.linear_bwd_weight(de, col, dwp, st.grad(ep + "projection.bias"))
+                    with ops._on_wgrad_stream(dwp):                  # same stream as the weight-gradient GEMM that fills dwp (ordered after it)
+                        if s == 0:
+                            gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))                       # layout plumbing back to [Co,Ci,kh,kw]
+                        else:
+                            gw.add_(dwp.view(gw.shape[0], gw.shape[2], gw.shape[3], gw.shape[1]).permute(0, 3, 1, 2))
             if s > 0:
                 dcol = ops.gemm_nt(de, self._wt(("embed", s)))
                 Hp = Wp = cfg.grid(s - 1)
                 dx = ops.col2im_tokens(dcol, Bn, cfg.embed_dim[s - 1], Hp, Wp, cfg.patch_stride[s], cfg.patch_padding[s])
             if on_stage_done is not None:
                 on_stage_done(s)
-        return None
+        return dpx
 
-    def _layer_bwd(self, dy, sv, s, l, H, W, tok0, prep, prescaled=False, out_scale=None):
+    def _layer_bwd(self, dy, sv, s, l, H, W, tok0, prep, prescaled=False, out_scale=None, need_wgrad=True):
         """prescaled: dy already carries this layer's second DropPath factor (the layer above wrote it so). out_scale: per-image factors the returned
-        gradient is multiplied with (the second DropPath of the layer below), applied by the last LayerNorm-backward kernel instead of a separate pass."""
+        gradient is multiplied with (the second DropPath of the layer below), applied by the last LayerNorm-backward kernel instead of a separate pass.
+        need_wgrad=False: the dX chain alone (see backward)."""
         cfg, st = self.cfg, self.s
         lp = self._stage(s) + f"layers.{l}."
         ap = lp + "attention.attention."
         Bn, L, C = dy.shape
         nh = cfg.num_heads[s]
         dy2 = dy.reshape(Bn * L, C)
-        g = st.grad
+        wg = need_wgrad
+        g = st.grad if wg else (lambda key: None)
         # MLP:  x3 = droppath2(x2 + W2 gelu(W1 h2 + b1) + b2)
         dp1, dp2 = sv["dp"]
         if dp2 is not None and not prescaled:
             dy2 = ops.dropout_add(dy2, None, 0.0, None, 0, L, row_scale=dp2)
-        ops.linear_bwd_weight(dy2, sv["g"], g(lp + "output.dense.weight"), g(lp + "output.dense.bias"))
+        if wg:
+            ops.linear_bwd_weight(dy2, sv["g"], g(lp + "output.dense.weight"), g(lp + "output.dense.bias"))
         du = ops.gemm_nt(dy2, self._wt(lp + "output.dense.weight"), act=2, aux=sv["u"])
-        ops.linear_bwd_weight(du, sv["h2"], g(lp + "intermediate.dense.weight"), g(lp + "intermediate.dense.bias"))
+        if wg:
+            ops.linear_bwd_weight(du, sv["h2"], g(lp + "intermediate.dense.weight"), g(lp + "intermediate.dense.bias"))
         dh2 = ops.gemm_nt(du, self._wt(lp + "intermediate.dense.weight"))
         dx2 = ops.layernorm_bwd(sv["x2"], dh2, st.f32(lp + "layernorm_after.weight"), sv["st2"], g(lp + "layernorm_after.weight"),
                                 g(lp + "layernorm_after.bias"), add=dy2, row_scale=None if dp1 is None else (dp1, L))
         dx2, da = dx2 if dp1 is not None else (dx2, dx2)
         # attention output projection: x2 = x + droppath(Wo ctx + bo)
-        ops.linear_bwd_weight(da, sv["ctx"].view(-1, C), g(lp + "attention.output.dense.weight"), g(lp + "attention.output.dense.bias"))
+        if wg:
+            ops.linear_bwd_weight(da, sv["ctx"].view(-1, C), g(lp + "attention.output.dense.weight"), g(lp + "attention.output.dense.bias"))
         dctx = ops.gemm_nt(da, self._wt(lp + "attention.output.dense.weight")).view(Bn, L, C)
         dq, dk, dv = ops.attention_bwd(sv["q"], sv["k"], sv["v"], sv["ctx"], dctx, sv["lse"], nh, C ** -0.5)
-        for name, d, inp in (("query", dq, sv["qc"]), ("key", dk, sv["kc"]), ("value", dv, sv["vc"])):
+        for name, d, inp in (("query", dq, sv["qc"]), ("key", dk, sv["kc"]), ("value", dv, sv["vc"])) if wg else ():
             ops.linear_bwd_weight(d.view(-1, C), inp.view(-1, C), g(ap + f"projection_{name}.weight"), g(ap + f"projection_{name}.bias"))
         # gradients wrt the three BatchNorm outputs, one grouped launch
         outs = ops.gemm_nt_group([(d.view(-1, C), self._wt(ap + f"projection_{name}.weight"), None) for name, d in (("query", dq), ("key", dk), ("value", dv))])
@@ -547,12 +566,15 @@ class CvtEncoderEngine:
             names = ("query", "key", "value")
             base = self._dwproj_params(s, l)
             bp = []
+            # frozen encoder: the kernels' by-products (dgamma, dbeta; the tap sums leave through the GS rows dwproj_dc_taps_ allocates) go to scratch
+            junk = None if wg else torch.empty((3, 2, C), dtype=torch.float32, device=dy.device)
             for n, b in zip(names, base):
                 cp = self._conv_prefix(s, l, n)
                 mean, rstd, _ = sv["bn"][n]
                 bp.append(dict(stride=b["stride"], taps=b["taps"], y=dcs[n], gamma=b["gamma"], mean=mean, rstd=rstd, beta=b["beta"],
                                yf=sv[{"query": "qc", "key": "kc", "value": "vc"}[n]] if self._bwd_stats_from_y else None,
-                               dgamma=g(cp + "normalization.weight"), dbeta=g(cp + "normalization.bias"), dw=g(cp + "convolution.weight").view(C, 9)))
+                               dgamma=g(cp + "normalization.weight") if wg else junk[len(bp), 0], dbeta=g(cp + "normalization.bias") if wg else junk[len(bp), 1],
+                               dw=g(cp + "convolution.weight").view(C, 9) if wg else None))
             coefs = ops.dwproj_bn_train_bwd_stats(h1, H, W, tok0, bp)
             for b, cf in zip(bp, coefs):
                 b["coef"] = cf
@@ -563,18 +585,22 @@ class CvtEncoderEngine:
             # the ordinary dx / tap-sum kernels with the raw taps
             arena = torch.empty((30, C), dtype=torch.float32, device=dy.device)     # 3 x tap-sum outputs
             raws = {n: self._raw_taps(s, l, n) for n in strides}
+            junk = None if wg else torch.empty((3, 2, C), dtype=torch.float32, device=dy.device)      # frozen encoder: (dgamma, dbeta) by-products
 
             def bproj(name):
                 cp = self._conv_prefix(s, l, name)
                 mean, rstd, _ = sv["bn"][name]
+                i = ("query", "key", "value").index(name)
                 return dict(wt=raws[name], dy=dcs[name], g=st.f32(cp + "normalization.weight"), mean=mean, rstd=rstd,
-                            dg=g(cp + "normalization.weight"), db=g(cp + "normalization.bias"))
+                            dg=g(cp + "normalization.weight") if wg else junk[i, 0], db=g(cp + "normalization.bias") if wg else junk[i, 1])
             coefs = dict(zip(("query",), ops.dwconv_bn_train_bwd_stats(h1, H, W, strides["query"], tok0, [bproj("query")])))
             coefs.update(zip(("key", "value"), ops.dwconv_bn_train_bwd_stats(h1, H, W, strides["key"], tok0, [bproj("key"), bproj("value")])))
             for i, name in enumerate(("query", "key", "value")):
                 cp = self._conv_prefix(s, l, name)
                 ops.dwconv_bn_train_dc_(h1, raws[name], coefs[name], dcs[name], H, W, strides[name], tok0)
                 projs.append((dcs[name], raws[name], strides[name]))
+                if not wg:
+                    continue
                 with ops._on_wgrad_stream(h1, dcs[name], arena):
                     G2, _ = ops.dwconv_bn_bwd_w(h1, dcs[name], H, W, strides[name], tok0, out=arena[10 * i:10 * i + 10])
                     ops.tap_grad_accum(G2, g(cp + "convolution.weight"))
@@ -585,6 +611,8 @@ class CvtEncoderEngine:
                 cp = self._conv_prefix(s, l, name)
                 wf, _ = self._fold_eval(s, l, name)
                 projs.append((dcs[name], wf, strides[name]))
+                if not wg:
+                    continue
                 with ops._on_wgrad_stream(h1, dcs[name], arena):
                     G, S = ops.dwconv_bn_bwd_w(h1, dcs[name], H, W, strides[name], tok0, out=arena[10 * i:10 * i + 10])
                     ops.bn_fold_bwd(st.f32(cp + "convolution.weight"), st.f32(cp + "normalization.weight"), st.f32(cp + "normalization.running_mean"),

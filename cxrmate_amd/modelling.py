@@ -226,9 +226,9 @@ class _EncodeFn(torch.autograd.Function):
         model._settle_owed_join()
         feats, saved = model._enc.forward(px, save=True)
         ctx.model, ctx.saved, ctx.nparams = model, saved, len(params)
-        # the stage-1 weight gradient is contracted against an im2col matrix that the BACKWARD builds from the pixels (the forward is an implicit
-        # GEMM): the caller's tensor is held by reference, so an in-place edit between forward and backward must be caught, as autograd's own
-        # saved-tensor version check would (px is not a differentiable input: save_for_backward has nothing to check it against)
+        # px is a differentiable input: backward returns its gradient when asked (pixel_values.grad). The stage-1 weight gradient is contracted
+        # against an im2col matrix that the BACKWARD builds from the pixels (the forward is an implicit GEMM): the caller's tensor is held by
+        # reference, so an in-place edit between forward and backward must be caught, as autograd's own saved-tensor version check would
         ctx.px, ctx.px_version = px, px._version
         return feats
 
@@ -239,19 +239,28 @@ class _EncodeFn(torch.autograd.Function):
         if ctx.px._version != ctx.px_version:
             raise RuntimeError("pixel_values was modified in place between the encoder forward and its backward (version "
                                f"{ctx.px_version} -> {ctx.px._version}): the patch-embedding weight gradient is computed from it in backward")
+        need_dpx = ctx.needs_input_grad[1]                                 # pixel_values.grad: the chain goes on through the stage-1 convolution
+        if ctx.nparams == 0:
+            # all-frozen encoder (entered for the pixels alone): the dX chain only -- no weight gradient is computed, the flat gradient buffer and
+            # every parameter's .grad stay as they are
+            with wgrad_overlap():
+                dpx = model._enc.backward(ctx.saved, dfeats.contiguous(), need_dpx=need_dpx, need_wgrad=False)
+                ops.wgrad_join()                                           # (nothing of the encoder's to wait for: ends what wgrad_begin() started)
+            ctx.saved = ctx.px = None
+            return (None, dpx)
         bound = model._grads_bindable("encoder.")
         if not model.direct_grads and bound != "accumulate":
             model.zero_grads_prefix("encoder.")
         with wgrad_overlap():                                              # weight-gradient GEMMs beside the dX chain, as in the fused step
-            model._enc.backward(ctx.saved, dfeats.contiguous())
+            dpx = model._enc.backward(ctx.saved, dfeats.contiguous(), need_dpx=need_dpx)
             if not bound:
                 ops.wgrad_join()                                           # ... complete before autograd reads them
             else:
                 model._queue_backward_join()
         ctx.saved = ctx.px = None
         if bound:
-            return (None, None) + model._bind_grads("encoder.", ctx.nparams)
-        return (None, None) + model._collect_grads("encoder.", ctx.nparams)
+            return (None, dpx) + model._bind_grads("encoder.", ctx.nparams)
+        return (None, dpx) + model._collect_grads("encoder.", ctx.nparams)
 
 
 class _DecodeFn(torch.autograd.Function):
@@ -550,6 +559,8 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
 
     # -------------------------------------------------------------------------------------- encoder
     def _pixels(self, pixel_values):
+        """-> fp32, contiguous, on the model's device. Converted with torch ops: when the caller's tensor requires a gradient, autograd carries the
+        encoder's pixel gradient back through them to `pixel_values.grad`, in the caller's dtype, shape and device."""
         px = pixel_values
         if px.device != self.device:
             px = px.to(self.device)
@@ -573,7 +584,8 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         multi = px.dim() == 5
         flat = px.view(-1, *px.shape[-3:]) if multi else px
         params = [p for _, p in self._grad_params("encoder.")]
-        if torch.is_grad_enabled() and params:
+        # under autograd: for a trainable encoder, or for pixel_values.grad alone (frozen encoder: the backward then runs the dX chain only)
+        if torch.is_grad_enabled() and (params or flat.requires_grad):
             feats = _EncodeFn.apply(self, flat, *params)
         else:
             feats, _ = self._enc.forward(flat, save=False)

@@ -655,6 +655,24 @@ def im2col_pixels(px, ks, stride, pad, kpad):
     return col, Ho, Wo
 
 
+def patch_embed_dgrad(de, w, Bn, H, W, ks, stride, pad, out=None):
+    """Data gradient of the stage-1 patch embedding: de [Bn*Ho*Wo, Co] bf16 (gradient of the convolution's output), w [Co, kpad] bf16 (the operand
+    the forward multiplies, K order of im2col_pixels) -> dpx [Bn, 3, H, W] fp32, every element written (csrc/conv.hip patch_embed_dgrad_kernel)."""
+    Cin = 3
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    assert de.dtype == BF16 and w.dtype == BF16 and de.is_contiguous() and w.is_contiguous()
+    assert w.dim() == 2 and w.shape[1] >= Cin * ks * ks and w.shape[0] % 8 == 0, tuple(w.shape)
+    Co, kpad = w.shape
+    if Bn <= 0 or Ho <= 0 or Wo <= 0 or tuple(de.shape) != (Bn * Ho * Wo, Co):
+        raise ValueError(f"patch_embed_dgrad: de {tuple(de.shape)} is not [{Bn} * {Ho} * {Wo}, {Co}]")
+    if not (de.is_cuda and w.is_cuda):
+        raise CxrError("cxrmate_amd kernels need CUDA(HIP) tensors; there is no CPU path")
+    dpx = out if out is not None else torch.empty((Bn, Cin, H, W), device=de.device, dtype=torch.float32)
+    assert dpx.dtype == torch.float32 and tuple(dpx.shape) == (Bn, Cin, H, W) and dpx.is_contiguous()
+    LIB.call("cxr_patch_embed_dgrad_f32", _p(de), _p(w), _p(dpx), Bn, Cin, H, W, Co, ks, stride, pad, Ho, Wo, kpad, _s())
+    return dpx
+
+
 def patch_embed_pack(w, out=None):
     """w [64, 3, 7, 7] fp32 -> the packed bf16 operand [64, 192] of patch_embed_s1 (K order (c, ky) x 8 taps, zero padded)"""
     assert w.dtype == torch.float32 and tuple(w.shape) == (64, 3, 7, 7) and w.is_contiguous()

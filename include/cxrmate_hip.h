@@ -196,6 +196,13 @@ int cxr_im2col_nchw_f32(const float* px, void* col, int Bn, int Cin, int H, int 
 int cxr_patch_embed_pack_f32(const float* w, void* out, hipStream_t stream);
 int cxr_patch_embed_s1_f32(const float* px, const void* Wpk, const float* bias, const float* gamma, const float* beta, float eps,
                            void* e_out, void* y_out, float* stats, int Bn, int H, int W, hipStream_t stream);
+/* Data gradient of the stage-1 patch embedding: what autograd's conv2d backward returns for the input of nn.Conv2d(3, Co, ks, stride, pad)
+ * (TF5 models/cvt/modeling_cvt.py:77-90), i.e. pixel_values.grad of the reference model. de [Bn*Ho*Wo, Co] bf16 (gradient of the convolution's
+ * output, token-major), w [Co, kpad] bf16 in the K order of cxr_im2col_nchw_f32 (the operand the forward multiplied) -> dpx [Bn, Cin, H, W] fp32,
+ * contiguous. Every element of dpx is WRITTEN (exact 0.0 where no output position covers the pixel), fp32 accumulation in a fixed order, no atomics.
+ * Requires Cin == 3, Co % 8 == 0, Ho / Wo consistent with (H, W, ks, stride, pad), 16-byte aligned de. */
+int cxr_patch_embed_dgrad_f32(const void* de, const void* w, float* dpx, int Bn, int Cin, int H, int W, int Co, int ks, int stride, int pad,
+                              int Ho, int Wo, int kpad, hipStream_t stream);
 int cxr_im2col_tok_bf16(const void* x, long x_bs, long x_rs, void* col, int Bn, int Cin, int H, int W, int stride, int pad, int Ho, int Wo,
                         hipStream_t stream);
 int cxr_col2im_tok_bf16(const void* dcol, void* dx, long dx_bs, long dx_rs, int Bn, int Cin, int H, int W, int stride, int pad, int Ho, int Wo,
