@@ -18,7 +18,7 @@ import os
 
 import torch
 
-from . import ops, weights
+from . import ops, weights, wgrad
 from .config import BertConfig
 
 BF16 = torch.bfloat16
@@ -250,7 +250,7 @@ class BertEngine:
             bt = self._bt.get(mode)
             if bt is None or bt[0] != sig:
                 bt = self._bt[mode] = (sig, ops.BatchedTranspose(srcs, pads), keys)
-            with ops._on_wgrad_stream():
+            with wgrad.on_stream():
                 bt[1].run()
             self._wt_ready = True
             self._wtb_ready = mode or self._wtb_ready
@@ -469,7 +469,7 @@ class BertEngine:
         scale = cfg.lora_alpha / cfg.lora_r
         dw = torch.zeros(st.f32(base + ".base_layer.weight").shape, dtype=torch.float32, device=dy.device)
         ops.linear_bwd_weight(dy, x, dw, st.grad(base + ".base_layer.bias"))
-        with ops._on_wgrad_stream(dw):                       # consumers of dw: same stream as the weight-gradient GEMM that fills it
+        with wgrad.on_stream(dw):                            # consumers of dw: same stream as the weight-gradient GEMM that fills it
             st.grad(base + ".base_layer.weight").add_(dw)
             dw16 = ops.cast_to_bf16(dw)
             # dB[n,r] = s * sum_k dW[n,k] A[r,k] ;  dA[r,k] = s * sum_n B[n,r] dW[n,k]
@@ -490,7 +490,7 @@ class BertEngine:
         ops.linear_bwd_weight(dy, x, st.grad(base + ".base_layer.weight"), st.grad(base + ".base_layer.bias"))
         B_l, A_l = st.w16(base + ".lora_B.default.weight"), st.w16(base + ".lora_A.default.weight")
         dt = ops.lora_down(dy, B_l, w_is_b=True, scale=s_)
-        with ops._on_wgrad_stream(dy, x, t, dt):
+        with wgrad.on_stream(dy, x, t, dt):
             ops.lora_outer_into(dy, t, st.grad(base + ".lora_B.default.weight"), cfg.lora_r, 1)                       # dB[n,r] += sum dy[m,n] t[m,r]
             ops.lora_outer_into(x, dt, st.grad(base + ".lora_A.default.weight"), 1, x.shape[1],                       # dA[r,k] += sum drop(x)[m,k] dt[m,r]
                                 drop=(cfg.lora_dropout, site), rows_per_b=T, seed=seed)
@@ -511,7 +511,7 @@ class BertEngine:
         dtq, dtk = ops.lora_down_multi([dict(x=dq, W=st.w16(bq + ".lora_B.default.weight"), w_is_b=True),
                                         dict(x=dk, W=st.w16(bk + ".lora_B.default.weight"), w_is_b=True)], scale=s_)
         K, r, pl = x.shape[1], cfg.lora_r, cfg.lora_dropout
-        with ops._on_wgrad_stream(dq, dk, x, tq, tk, dtq, dtk):
+        with wgrad.on_stream(dq, dk, x, tq, tk, dtq, dtk):
             ops.lora_outer_multi_into([dict(a=dq, t=tq, G=st.grad(bq + ".lora_B.default.weight"), g_ks=r, g_rs=1),                               # dB[n,r] += sum dy[m,n] t[m,r]
                                        dict(a=x, t=dtq, G=st.grad(bq + ".lora_A.default.weight"), g_ks=1, g_rs=K, drop=(pl, _site(l, 5))),        # dA[r,k] += sum drop(x)[m,k] dt[m,r]
                                        dict(a=dk, t=tk, G=st.grad(bk + ".lora_B.default.weight"), g_ks=r, g_rs=1),
@@ -529,8 +529,8 @@ class BertEngine:
         self.prepare()
         lora_tr = bool(saved.get("lora_tr"))
         self._prepare_transposes(lora_tr)
-        ops.wgrad_join()                                                # transposed weights (side stream) are ready
-        ops.wgrad_begin()                                               # from here on weight-gradient kernels run beside the main stream
+        wgrad.join()                                                    # transposed weights (side stream) are ready
+        wgrad.begin()                                                   # from here on weight-gradient kernels run beside the main stream
         st.ensure_grads()
         B, T = saved["B"], saved["T"]
         R, D, nh = B * T, cfg.hidden_size, cfg.num_attention_heads

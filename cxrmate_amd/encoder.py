@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import ops
+from . import ops, wgrad
 from .config import CvtConfig
 
 
@@ -211,9 +211,9 @@ class CvtEncoderEngine:
             sig = tuple(x.data_ptr() for x in srcs)
             if self._bt is None or self._bt_sig != sig:               # first use, or the store was re-packed (.to() / .cuda())
                 self._bt, self._bt_sig, self._bt_keys = ops.BatchedTranspose(srcs), sig, keys
-            with ops._on_wgrad_stream():
+            with wgrad.on_stream():
                 self._bt.run()
-            self._wt_event = ops.wgrad_mark()
+            self._wt_event = wgrad.mark()
             self._wt_ready = True
         for k, o in zip(self._bt_keys, self._bt.outs):
             prep[("wt", k)] = o
@@ -265,11 +265,11 @@ class CvtEncoderEngine:
                 xs = torch.empty((Bn, (px.shape[2] // 4) * (px.shape[3] // 4), C), dtype=torch.bfloat16, device=px.device)
                 _, e, estats, Ho, Wo = ops.patch_embed_s1(px, prep[("embed_pk", 0)], st.f32(ep + "projection.bias"), st.f32(ep + "normalization.weight"),
                                                           st.f32(ep + "normalization.bias"), cfg.inner_layer_norm_eps, need_e=save, out=xs.view(-1, C))
-                if save and _EARLY_PATCH_COL and ops.WGRAD_STREAM is not None:
+                if save and _EARLY_PATCH_COL and wgrad.stream() is not None:
                     # the im2col matrix of the PIXELS feeds the very last weight-gradient GEMM of the step; built where that GEMM is issued, its 100 us
                     # sit in the tail of the step with nothing on the main stream to hide them. It depends on the input alone: built now, on the
                     # weight-gradient stream, which has nothing else to do during the forward pass
-                    with ops._on_wgrad_stream(px):
+                    with wgrad.on_stream(px):
                         col = ops.im2col_pixels(px, cfg.patch_sizes[0], cfg.patch_stride[0], cfg.patch_padding[0], prep[("embed", 0)].shape[1])[0]
                         col_ev = torch.cuda.Event()
                         col_ev.record()                   # (the backward's last GEMM may read it from the main stream: see backward)
@@ -441,10 +441,10 @@ class CvtEncoderEngine:
         the weight-gradient stream; the flat gradient buffer is not touched (the scale / shift sums that the BatchNorm backward kernels produce
         as by-products go to scratch). Every dx is computed by the same launches on the same operands as with need_wgrad=True: the same bits."""
         cfg, st = self.cfg, self.s
-        ops.wgrad_begin()                                               # (also without weight gradients: the dX GEMMs pick the kernels they pick beside that stream)
+        wgrad.begin()                                                   # (also without weight gradients: the dX GEMMs pick the kernels they pick beside that stream)
         prep = self.prepare()
         self._prepare_transposes()
-        ops.wgrad_wait(self._wt_event)                                  # transposed weights are ready (NOT a join: the decoder's weight-gradient backlog keeps running)
+        wgrad.wait(self._wt_event)                                      # transposed weights are ready (NOT a join: the decoder's weight-gradient backlog keeps running)
         if need_wgrad:
             st.ensure_grads()
         grad = st.grad if need_wgrad else (lambda key: None)
@@ -490,25 +490,25 @@ class CvtEncoderEngine:
                 dwp = torch.zeros(wp.shape, dtype=torch.float32, device=de.device)
                 col = ss["col"]
                 if col is None:                                   # implicit-GEMM forward: the im2col matrix is built here, on the weight-gradient stream
-                    with ops._on_wgrad_stream(ss["xin"]):
+                    with wgrad.on_stream(ss["xin"]):
                         if s == 0:
                             col = ops.im2col_pixels(ss["xin"], cfg.patch_sizes[0], cfg.patch_stride[0], cfg.patch_padding[0], wp.shape[1])[0]
                         else:
                             col = ops.im2col_tokens(ss["xin"], ss["Hin"], ss["Win"], cfg.patch_stride[s], cfg.patch_padding[s])[0]
                 gw = st.grad(ep + "projection.weight")
-                if (s == 0 and _TAIL_ON_MAIN and ss.get("col_ev") is not None and ops.WGRAD_STREAM is not None and not ops._WGRAD_SKIP
+                if (s == 0 and _TAIL_ON_MAIN and ss.get("col_ev") is not None and wgrad.stream() is not None and not wgrad.scheduler.skip
                         and not torch.cuda.is_current_stream_capturing()):
                     # The step's LAST weight gradient (64 x 192 x 589824 at the benchmark batch, ~0.15 ms): its operand `de` is the main stream's last
                     # product, and on the weight-gradient stream it queues behind that stream's backlog of the stage-1 layer -- the main stream, which has
                     # nothing left to do, runs it instead, beside that backlog (profiles/r06_step_tail.txt: 0.33 ms of exposed tail per step before)
-                    ops.wgrad_flush()
+                    wgrad.flush()
                     torch.cuda.current_stream().wait_event(ss["col_ev"])
                     col.record_stream(torch.cuda.current_stream())
                     ops.gemm_tn(de, col, dwp, dbias=st.grad(ep + "projection.bias"))
                     gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))
                 else:
                     ops.linear_bwd_weight(de, col, dwp, st.grad(ep + "projection.bias"))
-                    with ops._on_wgrad_stream(dwp):                  # same stream as the weight-gradient GEMM that fills dwp (ordered after it)
+                    with wgrad.on_stream(dwp):                       # same stream as the weight-gradient GEMM that fills dwp (ordered after it)
                         if s == 0:
                             gw.add_(dwp[:, :gw[0].numel()].view(gw.shape))                       # layout plumbing back to [Co,Ci,kh,kw]
                         else:
@@ -601,7 +601,7 @@ class CvtEncoderEngine:
                 projs.append((dcs[name], raws[name], strides[name]))
                 if not wg:
                     continue
-                with ops._on_wgrad_stream(h1, dcs[name], arena):
+                with wgrad.on_stream(h1, dcs[name], arena):
                     G2, _ = ops.dwconv_bn_bwd_w(h1, dcs[name], H, W, strides[name], tok0, out=arena[10 * i:10 * i + 10])
                     ops.tap_grad_accum(G2, g(cp + "convolution.weight"))
             dh1 = ops.dwconv_bn_bwd_dx(projs, Bn, C, H, W, tok0)
@@ -613,7 +613,7 @@ class CvtEncoderEngine:
                 projs.append((dcs[name], wf, strides[name]))
                 if not wg:
                     continue
-                with ops._on_wgrad_stream(h1, dcs[name], arena):
+                with wgrad.on_stream(h1, dcs[name], arena):
                     G, S = ops.dwconv_bn_bwd_w(h1, dcs[name], H, W, strides[name], tok0, out=arena[10 * i:10 * i + 10])
                     ops.bn_fold_bwd(st.f32(cp + "convolution.weight"), st.f32(cp + "normalization.weight"), st.f32(cp + "normalization.running_mean"),
                                     st.f32(cp + "normalization.running_var"), cfg.bn_eps, G, S, g(cp + "convolution.weight"),

@@ -20,7 +20,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import ops, weights
+from . import ops, weights, wgrad
 from .config import EncoderDecoderConfig, from_hf_config
 from .decoder import BertEngine
 from .encoder import CvtEncoderEngine
@@ -234,7 +234,6 @@ class _EncodeFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeats):
-        from .training import wgrad_overlap
         model = ctx.model
         if ctx.px._version != ctx.px_version:
             raise RuntimeError("pixel_values was modified in place between the encoder forward and its backward (version "
@@ -243,18 +242,18 @@ class _EncodeFn(torch.autograd.Function):
         if ctx.nparams == 0:
             # all-frozen encoder (entered for the pixels alone): the dX chain only -- no weight gradient is computed, the flat gradient buffer and
             # every parameter's .grad stay as they are
-            with wgrad_overlap():
+            with wgrad.overlap():
                 dpx = model._enc.backward(ctx.saved, dfeats.contiguous(), need_dpx=need_dpx, need_wgrad=False)
-                ops.wgrad_join()                                           # (nothing of the encoder's to wait for: ends what wgrad_begin() started)
+                wgrad.join()                                               # (nothing of the encoder's to wait for: ends what wgrad.begin() started)
             ctx.saved = ctx.px = None
             return (None, dpx)
         bound = model._grads_bindable("encoder.")
         if not model.direct_grads and bound != "accumulate":
             model.zero_grads_prefix("encoder.")
-        with wgrad_overlap():                                              # weight-gradient GEMMs beside the dX chain, as in the fused step
+        with wgrad.overlap():                                              # weight-gradient GEMMs beside the dX chain, as in the fused step
             dpx = model._enc.backward(ctx.saved, dfeats.contiguous(), need_dpx=need_dpx)
             if not bound:
-                ops.wgrad_join()                                           # ... complete before autograd reads them
+                wgrad.join()                                               # ... complete before autograd reads them
             else:
                 model._queue_backward_join()
         ctx.saved = ctx.px = None
@@ -290,11 +289,10 @@ class _DecodeFn(torch.autograd.Function):
         B, T, V = dlogits.shape
         d16 = dlogits.reshape(B * T, V)
         d16 = ops.cast_to_bf16(d16.contiguous()) if d16.dtype == torch.float32 else d16.contiguous()
-        from .training import wgrad_overlap
-        with wgrad_overlap():
+        with wgrad.overlap():
             denc = model._dec.backward(ctx.saved, dlogits=d16, need_denc=ctx.need_denc)
             if not bound:
-                ops.wgrad_join()
+                wgrad.join()
             else:
                 model._queue_backward_join()                               # the decoder's weight gradients keep running under the encoder backward
         d_emb = None
@@ -524,14 +522,13 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         """One join of the weight-gradient stream at the end of the running backward pass (autograd final callback)."""
         if self.__dict__.get("_join_queued"):
             return
-        from .training import wgrad_overlap
-        side, cur = wgrad_overlap._stream, torch.cuda.current_stream(self.device)
+        side, cur = wgrad.owned_stream(), torch.cuda.current_stream(self.device)
         self.__dict__["_join_queued"] = True
 
         def done():
             self.__dict__["_join_queued"] = False
             with torch.cuda.stream(cur):
-                ops.wgrad_join(side)
+                wgrad.join(side)
 
         torch.autograd.Variable._execution_engine.queue_callback(done)
 
@@ -540,9 +537,8 @@ class _CXREncoderDecoderBase(ParamStore, GenerationMixin, TokenHelpers):
         _queue_backward_join() is still owed and the flag would keep every later backward pass from queueing its own: a new forward pass joins the
         weight-gradient stream itself and clears the flag (nothing to do in the normal case)."""
         if self.__dict__.get("_join_queued"):
-            from .training import wgrad_overlap
             self.__dict__["_join_queued"] = False
-            ops.wgrad_join(wgrad_overlap._stream)
+            wgrad.join(wgrad.owned_stream())
 
     def _collect_grads(self, prefix, n):
         """Gradients handed to autograd for the trainable parameters under `prefix`: views of ONE copy of the flat gradient range they span

@@ -9,7 +9,9 @@ import gc
 
 import torch
 
+from . import wgrad
 from ._lib import LIB, CxrError
+from .wgrad import raw_stream as _s
 
 BF16 = torch.bfloat16
 
@@ -20,22 +22,6 @@ def _p(t):
     if not t.is_cuda:
         raise CxrError("cxrmate_amd kernels need CUDA(HIP) tensors; there is no CPU path")
     return t.data_ptr()
-
-
-_DEV_INDEX = None
-
-
-_SIDE_RAW = None        # raw handle of the weight-gradient stream while wgrad_flush issues collected launches (see below)
-
-
-def _s():
-    """Raw hipStream_t of torch's current stream (fast path: no Stream object, no device queries -- this runs ~1500x per step)."""
-    global _DEV_INDEX
-    if _SIDE_RAW is not None:
-        return _SIDE_RAW
-    if _DEV_INDEX is None:
-        _DEV_INDEX = torch.cuda.current_device()
-    return torch._C._cuda_getCurrentRawStream(_DEV_INDEX)
 
 
 def _chk(t, dtype=None):
@@ -158,124 +144,31 @@ def colsum_into(x, out):
     LIB.call("cxr_colsum_bf16", _p(x), x.stride(0), _p(out), x.shape[0], x.shape[1], _s())
 
 
-_TN_WS = {}             # (device index, raw stream handle) -> fp32 scratch of the deterministic split-K weight-gradient GEMM (launches of one
-                        # stream are serial); 16 M floats (64 MB) cover every shape of this model: an output beyond it (splits * I_pad * J_pad floats, more than
-                        # 192 splits) falls back to fp32 atomics inside cxr_gemm_tn_bf16 -- reported once per shape, never silent
-_TN_WS_FLOATS = 16 << 20
-_TN_FALLBACK_SEEN = set()
-
-
-def _tn_ws(stream, device):
-    key = (device.index, stream)
-    ws = _TN_WS.get(key)
-    if ws is None:
-        ws = _TN_WS[key] = torch.empty(_TN_WS_FLOATS, dtype=torch.float32, device=device)
-    return ws
-
-
-def _tn_note_fallback(R, I, J):
-    """Warn when a shape cannot use the deterministic partial-tile path (the launch plan comes from the library: cxr_gemm_tn_plan)."""
-    import warnings
-    splits, need = _ct.c_int(0), _ct.c_long(0)
-    LIB.call("cxr_gemm_tn_plan", int(R), int(I), int(J), _ct.byref(splits), _ct.byref(need))
-    if splits.value > 1 and (need.value > _TN_WS_FLOATS or splits.value > 192) and (I, J) not in _TN_FALLBACK_SEEN:
-        _TN_FALLBACK_SEEN.add((I, J))
-        warnings.warn(f"weight-gradient GEMM {I}x{J} over {R} rows: {splits.value} splits need {need.value} scratch floats (> {_TN_WS_FLOATS}) -> fp32 "
-                      "atomics, the sum order (last bits of the gradient) is not reproducible for this shape")
-
-
-class _TnPending(_ct.Structure):
-    """cxr_tn_pending (include/cxrmate_hip.h): a weight gradient whose sum over the token splits is still to be added to C / dbias"""
-    _fields_ = [("ws", _ct.c_void_p), ("wsb", _ct.c_void_p), ("C", _ct.c_void_p), ("dbias", _ct.c_void_p), ("ldc", _ct.c_long),
-                ("I", _ct.c_int), ("J", _ct.c_int), ("Ip", _ct.c_int), ("Jp", _ct.c_int), ("splits", _ct.c_int), ("reserved", _ct.c_int)]
-
-
-# Deferred split sums of the weight-gradient stream (CXR_TN_DEFER=0: every GEMM followed by its own reduce launch, as before round 4). Each deferred
-# GEMM gets scratch of its own from a bump allocator over a few large buffers (288 GB of HBM: the ~2 GB of partial tiles a step leaves behind are not a
-# constraint); wgrad_reduce() adds all pending sums with one launch per 40 and hands the scratch back.
-_TN_DEFER = __import__("os").environ.get("CXR_TN_DEFER", "1") != "0"
-_TN_CHUNK = 64 << 20                                       # floats per arena buffer (256 MB)
-_TN_DEFER_FLOATS = int(__import__("os").environ.get("CXR_TN_DEFER_MB", "64")) << 18      # pending partial tiles that trigger a reduce launch (MB -> floats)
-_TN_ARENA = {}                                            # device index -> [buffers, index of the current one, floats used in it]
-_TN_PENDING = []                                          # (_TnPending, tensors kept alive)
-
-
-def _tn_arena_alloc(device, n):
-    ar = _TN_ARENA.get(device.index)
-    if ar is None:
-        ar = _TN_ARENA[device.index] = [[], 0, 0]
-    bufs = ar[0]
-    n = (n + 63) // 64 * 64
-    while True:
-        if ar[1] < len(bufs) and ar[2] + n <= bufs[ar[1]].numel():
-            out = bufs[ar[1]][ar[2]: ar[2] + n]
-            ar[2] += n
-            return out
-        if ar[1] < len(bufs):
-            ar[1] += 1
-            ar[2] = 0
-            continue
-        bufs.append(torch.empty(max(n, _TN_CHUNK), dtype=torch.float32, device=device))
-
-
-_TN_PENDING_PTRS = set()
-
-
-def wgrad_reduce(side=None):
-    """Add every pending split sum of the weight-gradient stream to its gradient (one launch per 40 sums, on that stream, behind the GEMMs that left
-    the partial tiles). Called at every point where something may READ a weight gradient: the joins, the fork points of the gradient all-reduce and of
-    the early optimiser update, other side-stream work that consumes a GEMM's result, the end of a wgrad_overlap context."""
-    if not _TN_PENDING:
-        return
-    side = WGRAD_STREAM if side is None else side
-    assert side is not None, "pending weight-gradient sums outlived their stream"
-    arr = (_TnPending * len(_TN_PENDING))(*[d for d, _ in _TN_PENDING])
-    LIB.call("cxr_gemm_tn_reduce_batch", _ct.addressof(arr), len(_TN_PENDING), side.cuda_stream)
-    _TN_PENDING.clear()
-    _TN_PENDING_PTRS.clear()
-    for ar in _TN_ARENA.values():
-        ar[1] = ar[2] = 0                                  # the same stream orders the next GEMM's partial tiles behind this reduce
-
-
 def gemm_tn(p, q, out, dbias=None, alpha=1.0):
     """out[I,J] (fp32) += alpha * p[R,I]^T @ q[R,J];  dbias[I] += colsum(p). p, q bf16 row-major (row stride free). Issued from the weight-gradient
-    stream's deferred launches (wgrad_flush) the sum over the token splits stays pending until wgrad_reduce()."""
+    stream's deferred launches (wgrad.flush) the sum over the token splits stays pending until wgrad.reduce()."""
     _chk(p, BF16); _chk(q, BF16)
     R, I = p.shape
     R2, J = q.shape
     assert R == R2 and out.dtype == torch.float32 and out.shape == (I, J) and out.stride(1) == 1
     prof = GEMM_PROFILE
     if prof is not None:
-        pstream = WGRAD_STREAM if _SIDE_RAW is not None else None           # the stream the kernel is launched on
+        pstream = wgrad.scheduler.issuing()                                  # the stream the kernel is launched on
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(pstream)
     stream = _s()
-    # The batched reduce adds every pending split sum with a plain read-modify-write of its destination: two entries of one batch that name the
-    # same C (a weight used twice in one backward, tied / shared parameters), or a one-split launch adding into a C whose sum is still pending,
-    # would race. A destination that is already pending is settled first (stream order then serialises the two, as before the deferral).
-    if _TN_PENDING_PTRS and (out.data_ptr() in _TN_PENDING_PTRS or (dbias is not None and dbias.data_ptr() in _TN_PENDING_PTRS)):
-        wgrad_reduce()
-    if _TN_DEFER and _SIDE_RAW is not None and WGRAD_STREAM is not None:
+    sched = wgrad.scheduler
+    sched.tn_settle_dest(out, dbias)
+    if sched.tn_deferring():
         splits, need = _ct.c_int(0), _ct.c_long(0)
         LIB.call("cxr_gemm_tn_plan", int(R), int(I), int(J), _ct.byref(splits), _ct.byref(need))
-        ws = _tn_arena_alloc(p.device, need.value) if (splits.value > 1 and need.value > 0) else None
-        pend = _TnPending()
+        ws = sched.tn_scratch(p.device, need.value) if (splits.value > 1 and need.value > 0) else None
+        pend = wgrad.TnPending()
         LIB.call("cxr_gemm_tn_partial_bf16", _p(p), p.stride(0), _p(q), q.stride(0), _p(out), out.stride(0), _p(dbias), R, I, J, float(alpha), _p(ws),
                  0 if ws is None else ws.numel(), _ct.byref(pend), stream)
-        if pend.splits > 1:
-            _TN_PENDING.append((pend, (out, dbias)))
-            _TN_PENDING_PTRS.add(out.data_ptr())
-            if dbias is not None:
-                _TN_PENDING_PTRS.add(dbias.data_ptr())
-            # ... but not for long: the partial tiles should still be in the 256-MB Infinity Cache when the reduce reads them (with every sum of a
-            # step pending, ~2 GB of partial tiles went out to HBM and came back: the step got 0.16 ms SLOWER than with one reduce launch per GEMM)
-            ar = _TN_ARENA[p.device.index]
-            if len(_TN_PENDING) >= 40 or ar[1] > 0 or ar[2] >= _TN_DEFER_FLOATS:
-                wgrad_reduce()
+        sched.tn_add_pending(pend, out, dbias)
     else:
-        ws = _tn_ws(stream, p.device)
-        if (I, J) not in _TN_FALLBACK_SEEN and I * J > (1 << 20):
-            _tn_note_fallback(R, I, J)
+        ws = sched.tn_scratch_immediate(stream, p.device, R, I, J)
         LIB.call("cxr_gemm_tn_bf16", _p(p), p.stride(0), _p(q), q.stride(0), _p(out), out.stride(0), _p(dbias), R, I, J, float(alpha), _p(ws), ws.numel(),
                  stream)
     if prof is not None:
@@ -284,150 +177,11 @@ def gemm_tn(p, q, out, dbias=None, alpha=1.0):
     return out
 
 
-# Weight-gradient work (split-K TN GEMMs, depthwise-conv tap sums) only feeds the optimiser, never the dX chain: when WGRAD_STREAM is
-# set (training.py) it is issued on that side stream so that these atomics-/latency-bound kernels overlap the MFMA-bound dX GEMMs and
-# attention kernels of the main stream. The side stream waits for the main stream's current position (operands are ready), operands
-# are pinned with record_stream, and the step joins the side stream before the all-reduce / optimiser (wgrad_join).
-WGRAD_STREAM = None
-
-
-class _on_wgrad_stream:
-    def __init__(self, *tensors):
-        self.tensors = tensors
-
-    def __enter__(self):
-        self.side = WGRAD_STREAM
-        if self.side is not None:
-            wgrad_flush()                                  # (launches collected by _side_defer come first on the side stream)
-            wgrad_reduce()                                 # (... and what follows on that stream may read a weight gradient)
-            self.side.wait_stream(torch.cuda.current_stream())
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.side is not None:
-            self.ctx.__exit__(*exc)
-            for t in self.tensors:
-                if t is not None:
-                    t.record_stream(self.side)
-        return False
-
-
-_WGRAD_BATCH = max(1, int(__import__("os").environ.get("CXR_WGRAD_BATCH", "4")))
-_SIDE_DEFERRED = []     # launches waiting for the next fork point (closures issuing C-ABI launches on the side stream)
-_SIDE_PENDING = []      # their operands, kept alive until the next wgrad_join()
-
-
-def _side_defer(fn, *tensors):
-    """Issue `fn` (C-ABI launches only, nothing allocated) on the weight-gradient stream. Ordering against the main stream costs an event record
-    on the MAIN stream -- a barrier packet that keeps the next main-stream kernel from starting under the tail of the previous one: ~9 us each,
-    145 of them = 1.3 ms of a 41-ms step when every weight-gradient launch had its own. The launches are therefore collected and issued in
-    batches of CXR_WGRAD_BATCH behind ONE event (wgrad_flush); every synchronisation with the side stream flushes first. Operands are kept alive
-    until the next wgrad_join() instead of record_stream (after the join nothing on the side stream can still read them); as before, nothing may
-    overwrite an operand in place before that join -- the side stream runs arbitrarily far behind the main stream."""
-    if WGRAD_STREAM is None:
-        fn()
-        return
-    _SIDE_DEFERRED.append(fn)
-    _SIDE_PENDING.append(tensors)
-    if len(_SIDE_DEFERRED) >= _WGRAD_BATCH:
-        wgrad_flush()
-
-
-def wgrad_flush():
-    """Issue the collected weight-gradient launches: one event on the main stream (their operands are complete), the side stream waits for it."""
-    global _SIDE_RAW
-    if not _SIDE_DEFERRED:
-        return
-    side = WGRAD_STREAM
-    assert side is not None, "deferred weight-gradient launches outlived their stream (wgrad_overlap exits through wgrad_flush)"
-    ev = torch.cuda.Event()
-    ev.record()
-    side.wait_event(ev)
-    _SIDE_RAW = side.cuda_stream
-    try:
-        for fn in _SIDE_DEFERRED:
-            fn()
-    finally:
-        _SIDE_RAW = None
-        _SIDE_DEFERRED.clear()
-
-
-def wgrad_discard():
-    """Drop collected launches without issuing them (error path of training.wgrad_overlap)."""
-    _SIDE_DEFERRED.clear()
-    _SIDE_PENDING.clear()
-    _TN_PENDING.clear()
-    _TN_PENDING_PTRS.clear()
-    for ar in _TN_ARENA.values():
-        ar[1] = ar[2] = 0
-
-
-def wgrad_join(stream=None):
-    """stream: the weight-gradient stream to join when called outside the wgrad_overlap context that launched on it (deferred joins)"""
-    wgrad_flush()
-    stream = WGRAD_STREAM if stream is None else stream
-    wgrad_reduce(stream)
-    if stream is not None:
-        torch.cuda.current_stream().wait_stream(stream)
-    _SIDE_PENDING.clear()
-    gemm_exclusive(True)                                   # nothing runs beside the main stream any more
-
-
-_GEMM_EXCLUSIVE = True
-
-
-def gemm_exclusive(on: bool):
-    """on: NT GEMM launches may use the persistent one-workgroup-per-CU kernels (csrc/gemm_ws.hip, gemm_pk.hip: 144 KB of LDS each). The backward
-    passes turn it off while weight-gradient kernels run beside the main stream (wgrad_begin) -- such a workgroup cannot share a CU with them
-    and the kernels' static work partition would wait for the last CU to free up (measured: 43.9 -> 45.8 ms per step)."""
-    global _GEMM_EXCLUSIVE
-    if bool(on) != _GEMM_EXCLUSIVE:
-        _GEMM_EXCLUSIVE = bool(on)
-        LIB.call("cxr_gemm_set_exclusive", int(bool(on)))
-
-
-_EXCL_ALWAYS = __import__("os").environ.get("CXR_GEMM_EXCL_ALWAYS") == "1"      # lab switch: persistent GEMM kernels also beside the weight-gradient stream
-
-
-def wgrad_begin():
-    """Start of a backward pass: from here on weight-gradient kernels may be running on the side stream (until wgrad_join)."""
-    if WGRAD_STREAM is not None and not _EXCL_ALWAYS:
-        gemm_exclusive(False)
-
-
-def wgrad_mark():
-    """Event at the side stream's current position (None without a side stream): lets a later consumer wait for exactly the work issued so far
-    (the W^T transposes of a forward pass) instead of joining the whole weight-gradient backlog."""
-    if WGRAD_STREAM is None:
-        return None
-    wgrad_flush()
-    wgrad_reduce()
-    ev = torch.cuda.Event()
-    ev.record(WGRAD_STREAM)
-    return ev
-
-
-def wgrad_wait(ev):
-    if ev is not None:
-        torch.cuda.current_stream().wait_event(ev)
-
-
-_WGRAD_SKIP = __import__("os").environ.get("CXR_WGRAD_SKIP") == "1"       # TIMING EXPERIMENT ONLY (wrong gradients): no weight-gradient GEMM is launched
-if _WGRAD_SKIP:
-    if __import__("os").environ.get("CXR_DEBUG_TIMING") != "1":
-        raise RuntimeError("CXR_WGRAD_SKIP=1 drops every Linear weight gradient (a timing experiment): it is only honoured together with "
-                           "CXR_DEBUG_TIMING=1")
-    __import__("warnings").warn("CXR_WGRAD_SKIP=1: NO Linear weight gradient is computed in this process -- timing experiment, training results are wrong",
-                                RuntimeWarning, stacklevel=1)
-
-
 def linear_bwd_weight(dy, x, dw, db=None):
-    """dw[N,K] += dy[M,N]^T @ x[M,K]; db[N] += colsum(dy)   (one split-K TN kernel; no transposes)."""
-    if _WGRAD_SKIP:
+    """dw[N,K] += dy[M,N]^T @ x[M,K]; db[N] += colsum(dy)   (one split-K TN kernel; no transposes). Goes to the weight-gradient stream (wgrad.py)."""
+    if wgrad.scheduler.skip:
         return
-    _side_defer(lambda: gemm_tn(dy, x, dw, dbias=db), dy, x, dw, db)
+    wgrad.defer(lambda: gemm_tn(dy, x, dw, dbias=db), dy, x, dw, db)
 
 
 def linear_bwd_input(dy, w_t, **kw):
@@ -634,14 +388,14 @@ def layernorm_bwd(x, dy, gamma, stats, dgamma, dbeta, add=None, out=None, drop=N
     if dgamma is not None:
         nb = LIB.load().cxr_layernorm_bwd_grid(rows, C)
         ws = torch.empty((nb, 2, C), device=x.device, dtype=torch.float32)
-    side = WGRAD_STREAM is not None and dgamma is not None       # row sum of the (dgamma, dbeta) partials off the critical path
+    side = wgrad.stream() is not None and dgamma is not None       # row sum of the (dgamma, dbeta) partials off the critical path
     LIB.call("cxr_layernorm_bwd_bf16", _p(x), x.stride(0), _p(dy), dy.stride(0), _p(gamma), _p(stats), _p(add),
              add.stride(0) if add is not None else 0, _p(out), out.stride(0) if out is not None else C, None if side else _p(dgamma), None if side else _p(dbeta), _p(ws), rows, C, _p(out2),
              out2.stride(0) if second else 0, float(drop[0]) if drop is not None else 0.0, _p(drop[1]) if drop is not None else None,
              int(drop[2]) if drop is not None else 0, int(drop[3]) if drop is not None else (int(row_scale[1]) if row_scale is not None else 1),
              int(drop[4]) if drop is not None else 0, _p(row_scale[0]) if row_scale is not None else None, _s())
     if side:
-        _side_defer(lambda: LIB.call("cxr_layernorm_bwd_reduce", _p(ws), rows, C, _p(dgamma), _p(dbeta), _s()), ws, dgamma, dbeta)
+        wgrad.defer(lambda: LIB.call("cxr_layernorm_bwd_reduce", _p(ws), rows, C, _p(dgamma), _p(dbeta), _s()), ws, dgamma, dbeta)
     return (out, out2) if second else out
 
 
@@ -1013,7 +767,7 @@ def bert_embed(ids, tt, pid, word, typ, posw, gamma, beta, eps, T, pos_offset=0,
 
 def bert_embed_bwd(dsum, ids, tt, pid, dword, dtype_, dpos, T, pos_offset, padding_idx):
     # embedding-table gradients only feed the optimiser: weight-gradient stream
-    _side_defer(lambda: LIB.call("cxr_bert_embed_bwd", _p(dsum), _p(ids), _p(tt), _p(pid), _p(dword), _p(dtype_), _p(dpos), ids.numel(), T, pos_offset,
+    wgrad.defer(lambda: LIB.call("cxr_bert_embed_bwd", _p(dsum), _p(ids), _p(tt), _p(pid), _p(dword), _p(dtype_), _p(dpos), ids.numel(), T, pos_offset,
                                  int(padding_idx), dsum.shape[1], _s()), dsum, ids, tt, pid, dword, dtype_, dpos)
 
 

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import torch
 
-from . import dp, ops
+from . import dp, ops, wgrad
 
 
 _SIDE = {}
@@ -149,10 +149,9 @@ def scst_step(model, opt, reward_fn, images, prompt_ids, label_texts, special, d
         loss, _, dl = ops.softmax_ce(flat, labels, pad, w, thr=thr)
         if temperature != 1.0:
             dl.mul_(1.0 / temperature)
-        from .training import wgrad_overlap
-        with wgrad_overlap():                                                # weight-gradient GEMMs beside the dX chain, as in the TF step
+        with wgrad.overlap():                                                # weight-gradient GEMMs beside the dX chain, as in the TF step
             model._dec.backward(saved, dlogits=dl, need_denc=False)
-            ops.wgrad_join()
+            wgrad.join()
         _mark("backward queued + joined")
         world = dp.world_size()
         if dp.active():

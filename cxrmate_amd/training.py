@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import dp, ops
+from . import dp, ops, wgrad
 
 
 class FusedAdamW:
@@ -80,7 +80,7 @@ def _phase_fwd_loss_decbwd(model, opt, px, ids, am, tt, lab, pad_token_id, pos, 
     """zero grads -> encoder fwd -> decoder fwd -> fused CE (loss + dlogits) -> decoder bwd. Returns (loss, esaved, denc)."""
     dev = model.device
     if zero:
-        side = ops.WGRAD_STREAM
+        side = wgrad.stream()
         if side is not None and _ZERO_ON_SIDE:
             # the gradient buffer is not touched before the decoder backward, which starts by joining the weight-gradient stream: the five fill
             # kernels (0.1 ms) run there, under the forward pass
@@ -113,45 +113,20 @@ def _phase_fwd_loss_decbwd(model, opt, px, ids, am, tt, lab, pad_token_id, pos, 
         dl = full.view(Bq * T, -1)
     denc = model._dec.backward(dsaved, dlogits=dl, need_denc=enc_trainable)
     if join:
-        ops.wgrad_join()                  # decoder weight gradients complete (graph capture needs the fork joined; an all-reduce may start now)
+        wgrad.join()                      # decoder weight gradients complete (graph capture needs the fork joined; an all-reduce may start now)
     return loss, esaved, denc
 
 
 def _phase_encbwd(model, esaved, denc, on_stage_done=None):
     if esaved is not None:
         model._enc.backward(esaved, denc.view(-1, denc.shape[-1]), on_stage_done=on_stage_done)
-    ops.wgrad_join()
+    wgrad.join()
 
 
 _ZERO_ON_SIDE = os.environ.get("CXR_ZERO_ON_SIDE", "1") != "0"              # A/B switch: 0 = gradient zeroing on the main stream
 _EARLY_DEC_ADAMW = os.environ.get("CXR_EARLY_DEC_ADAMW", "1") != "0"      # A/B switch: 0 = one AdamW launch at the end of the step
 _EARLY_ENC_ADAMW = os.environ.get("CXR_EARLY_ENC_ADAMW", "1") != "0"      # A/B switch: 0 = the whole encoder range updated at the end of the step
 _BF16_LOGITS = os.environ.get("CXR_BF16_LOGITS", "1") != "0"      # training step: bf16 logits as under the reference's autocast (0: fp32)
-
-
-class wgrad_overlap:
-    """Context: run weight-gradient kernels on a side stream (see ops.WGRAD_STREAM)."""
-    _stream = None
-
-    def __enter__(self):
-        if wgrad_overlap._stream is None and os.environ.get("CXR_WGRAD_OVERLAP", "1") != "0":      # 0: A/B switch, everything on one stream
-            # CXR_WGRAD_PRIORITY: stream priority of the weight-gradient stream (default: torch's default = lowest; negative = higher)
-            prio = int(os.environ.get("CXR_WGRAD_PRIORITY", "0"))
-            wgrad_overlap._stream = torch.cuda.Stream(priority=prio)
-        ops.wgrad_flush()
-        self.prev, ops.WGRAD_STREAM = ops.WGRAD_STREAM, wgrad_overlap._stream
-        return self
-
-    def __exit__(self, *exc):
-        try:
-            if exc[0] is None:
-                ops.wgrad_flush()                           # launches still collected for this stream are issued on it
-                ops.wgrad_reduce()                          # ... and the split sums they left pending are added (one launch)
-            else:
-                ops.wgrad_discard()                         # the step failed: nothing of it is launched later by an unrelated step
-        finally:
-            ops.WGRAD_STREAM = self.prev
-        return False
 
 
 def tf_train_step(model, opt: FusedAdamW, pixel_values, decoder_input_ids, decoder_attention_mask, decoder_token_type_ids, label_ids,
@@ -161,7 +136,7 @@ def tf_train_step(model, opt: FusedAdamW, pixel_values, decoder_input_ids, decod
     mbatch_size 8, accumulated_mbatch_size 32; under DDP Lightning wraps the first k - 1 micro-steps in `no_sync()`): micro-step 0 zeroes the
     gradient buffer, every micro-step adds its gradients, ONLY the last one all-reduces (once per optimiser step, not once per micro-batch) and
     runs AdamW on the mean over ranks and micro-batches (gscale = 1 / (world * k))."""
-    with wgrad_overlap():
+    with wgrad.overlap():
         return _tf_train_step(model, opt, pixel_values, decoder_input_ids, decoder_attention_mask, decoder_token_type_ids, label_ids,
                               pad_token_id, decoder_position_ids, logits_slice_from, accumulate)
 
@@ -183,27 +158,24 @@ def _tf_train_step(model, opt, pixel_values, decoder_input_ids, decoder_attentio
     if sync and enc_trainable:
         # decoder parameters sit after the encoder's in the flat buffer: reduce them while the encoder backward runs (the reducer's stream
         # waits for the weight-gradient stream, the main stream does not)
-        ops.wgrad_flush()
-        ops.wgrad_reduce()
-        opt.reducer.reduce_range(opt.split, model._param_total, after=ops.WGRAD_STREAM)
+        wgrad.settle()
+        opt.reducer.reduce_range(opt.split, model._param_total, after=wgrad.stream())
     early = None
     if sync and enc_trainable and opt.enc_tail:
         # ... and every encoder stage as soon as its backward is through (the last stage + projection head first: 93 % of the encoder's parameters),
         # while the earlier stages are still in backward; stage 0 is picked up by the closing reduce_range below
         def early(s):
             if s != min(opt.stage_start):
-                ops.wgrad_flush()
-                ops.wgrad_reduce()
-                opt.reducer.reduce_range(*opt.stage_range(s), after=ops.WGRAD_STREAM)
+                wgrad.settle()
+                opt.reducer.reduce_range(*opt.stage_range(s), after=wgrad.stream())
     gscale = 1.0 / (world * k)
-    side = ops.WGRAD_STREAM
+    side = wgrad.stream()
     dec_early = _EARLY_DEC_ADAMW and not sync and enc_trainable and side is not None
     if dec_early:
         # one rank: the decoder's gradients are final once its weight-gradient kernels are through -- its 81 M parameters (0.43 ms of AdamW at the
         # HBM rate) are updated on the weight-gradient stream, behind those kernels, while the main stream runs the encoder backward. Nothing
         # reads decoder weights before the next forward; the join at the end of the encoder backward orders the update before it.
-        ops.wgrad_flush()
-        ops.wgrad_reduce()                                         # the decoder's pending split sums: ONE launch, in front of the update
+        wgrad.settle()                                             # the decoder's pending split sums: ONE launch, in front of the update
         side.wait_stream(torch.cuda.current_stream())              # every decoder dX kernel (they read the weights) is in front of the update
         with torch.cuda.stream(side):
             opt.step(gscale=gscale, lo_bound=opt.split, begin=True, finish=False)
@@ -216,8 +188,7 @@ def _tf_train_step(model, opt, pixel_values, decoder_input_ids, decoder_attentio
         def early(s):
             nonlocal enc_hi
             if s == opt.enc_last_stage and last_lo > 0:
-                ops.wgrad_flush()
-                ops.wgrad_reduce()
+                wgrad.settle()
                 side.wait_stream(torch.cuda.current_stream())      # the stage's dX kernels (weight readers) and main-stream parameter-gradient writers
                 with torch.cuda.stream(side):
                     opt.step(gscale=gscale, lo_bound=last_lo, hi_bound=last_hi, begin=False, finish=False)
@@ -257,7 +228,7 @@ class GraphedTFStep:
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         self.g1, self.g2, self.g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with wgrad_overlap():
+        with wgrad.overlap():
             with ops.graph_capture(self.g1, pool=pool):
                 self.loss, self._esaved, self._denc = _phase_fwd_loss_decbwd(model, opt, px, ids, am, tt, lab, pad_token_id, pos, 0)
             with ops.graph_capture(self.g2, pool=pool):

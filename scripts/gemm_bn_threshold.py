@@ -2,8 +2,8 @@
 """128x128 against 128x64 tiles of gemm_nt_kernel for problems of 160 .. 300 128-wide tiles (run twice: default and CXR_GEMM_BN=64; the tile kernels only)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cxrmate_amd import ops
-ops.gemm_exclusive(False)
+from cxrmate_amd import ops, wgrad
+wgrad.exclusive(False)
 BF = torch.bfloat16
 for N, K in ((384, 384), (768, 768), (384, 1536), (1536, 384)):
     for tiles in (128, 162, 192, 219, 240, 255, 288, 320):

@@ -2,9 +2,9 @@
 """NT GEMM shapes of the SCST re-scoring pass and of the reward model (about 4096 rows), alone: python scripts/r4/gemm_small_m.py   (CXR_GEMM_STAGES / CXR_GEMM_BN select the kernel)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from cxrmate_amd import ops
+from cxrmate_amd import ops, wgrad
 BF = torch.bfloat16
-ops.gemm_exclusive(False)
+wgrad.exclusive(False)
 shapes = [(4080, 768, 768, 0), (4080, 768, 768, 1), (4096, 2304, 768, 0), (4096, 3072, 768, 2), (4096, 768, 3072, 1), (2048, 768, 768, 1), (8192, 768, 768, 1)]
 for M, N, K, mode in shapes:
     nb = 8

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""(round 5: the backward runs inside training.wgrad_overlap() as in scst.scst_step -- the round-4 script ran it on one stream, which is why its
+"""(round 5: the backward runs inside wgrad.overlap() as in scst.scst_step -- the round-4 script ran it on one stream, which is why its
 kernel table showed 49 un-batched gemm_tn_reduce_kernel launches that the step itself does not issue.)
 The re-scoring phase of the SCST step alone (TF forward over the sampled rows, REINFORCE loss, decoder backward), 10 times: run under
 rocprofv3 --kernel-trace --stats for its kernel table."""
@@ -9,7 +9,7 @@ from cxrmate_amd.config import EncoderDecoderConfig
 from cxrmate_amd.modelling import LongitudinalPromptMultiCXREncoderDecoderModel
 from cxrmate_amd.reward import CXRBERTReward
 from cxrmate_amd.training import FusedAdamW
-from cxrmate_amd import ops
+from cxrmate_amd import ops, wgrad
 
 dev = torch.device("cuda")
 B, N = 16, 2
@@ -59,9 +59,8 @@ with torch.no_grad():
         labels = s2[:, P:].reshape(-1)
         w = ops.ce_weights(labels, 4, mode=1, reward=torch.ones(Bq, device=dev), T=n_new)
         loss, _, dl = ops.softmax_ce(flat, labels, 4, w, thr=thr)
-        from cxrmate_amd.training import wgrad_overlap
-        with wgrad_overlap():                                 # as scst.scst_step: weight-gradient GEMMs on the side stream, their split sums added by batched launches
+        with wgrad.overlap():                                 # as scst.scst_step: weight-gradient GEMMs on the side stream, their split sums added by batched launches
             m._dec.backward(saved, dlogits=dl, need_denc=False)
-            ops.wgrad_join()
+            wgrad.join()
     torch.cuda.synchronize()
     T("re-score: TF fwd + REINFORCE loss + decoder bwd", rescore, 10)

@@ -6,7 +6,7 @@ from cxrmate_amd.config import EncoderDecoderConfig
 from cxrmate_amd.modelling import LongitudinalPromptMultiCXREncoderDecoderModel
 from cxrmate_amd.reward import CXRBERTReward
 from cxrmate_amd.training import FusedAdamW
-from cxrmate_amd import ops
+from cxrmate_amd import ops, wgrad
 
 dev = torch.device("cuda")
 B, N = 16, 2
@@ -58,6 +58,6 @@ with torch.no_grad():
         w = ops.ce_weights(labels, 4, mode=1, reward=torch.ones(Bq, device=dev), T=n_new)
         loss, _, dl = ops.softmax_ce(flat, labels, 4, w, thr=thr)
         m._dec.backward(saved, dlogits=dl, need_denc=False)
-        ops.wgrad_join()
+        wgrad.join()
     T("re-score: TF fwd + REINFORCE loss + decoder bwd", rescore)
     T("AdamW, 80.9 M decoder parameters", lambda: opt.step())

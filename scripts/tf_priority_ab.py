@@ -7,7 +7,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from cxrmate_amd import training  # noqa: E402
+from cxrmate_amd import wgrad  # noqa: E402
 from cxrmate_amd.config import EncoderDecoderConfig  # noqa: E402
 from cxrmate_amd.modelling import MultiCXREncoderDecoderModel  # noqa: E402
 from cxrmate_amd.training import FusedAdamW, tf_train_step  # noqa: E402
@@ -21,7 +21,7 @@ tt = model.token_ids_to_token_type_ids(inp, [3])
 
 
 def run(main_prio, side_prio, n=8):
-    training.wgrad_overlap._stream = torch.cuda.Stream(priority=side_prio)
+    wgrad.scheduler.owned = torch.cuda.Stream(priority=side_prio)
     ms = torch.cuda.Stream(priority=main_prio) if main_prio is not None else torch.cuda.current_stream()
     ms.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(ms):

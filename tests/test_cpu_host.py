@@ -297,20 +297,45 @@ def test_reward_and_chexbert_constructors_follow_the_reference_signatures(tmp_pa
 
 
 def test_failed_step_leaves_no_deferred_weight_gradient_launches(monkeypatch):
-    """training.wgrad_overlap collects weight-gradient launches (ops._side_defer) and issues them in batches; a step that raises must not leave
-    launches behind for the next step to issue, and the stream selection is restored."""
-    from cxrmate_amd import ops, training
+    """wgrad.overlap() collects weight-gradient launches (wgrad.defer) and issues them in batches; a step that raises must not leave launches,
+    kept operands or pending split sums (their destinations, their scratch) behind for the next step, and the stream selection is restored."""
+    from cxrmate_amd import wgrad
+    sch = wgrad.scheduler
     monkeypatch.setenv("CXR_WGRAD_OVERLAP", "0")                    # no GPU here: the context runs without a side stream
     ran = []
-    ops._side_defer(lambda: ran.append(1))                            # no side stream: runs inline
-    assert ran == [1] and not ops._SIDE_DEFERRED
-    prev = ops.WGRAD_STREAM
+    wgrad.defer(lambda: ran.append(1))                                # no side stream: runs inline
+    assert ran == [1] and not sch.deferred
+    prev = wgrad.stream()
+    monkeypatch.setitem(sch.tn_arena, 0, [[], 0, 0])
     with pytest.raises(ValueError):
-        with training.wgrad_overlap():
-            ops._SIDE_DEFERRED.append(lambda: ran.append(2))          # (as if collected for a side stream)
-            ops._SIDE_PENDING.append(())
+        with wgrad.overlap():
+            sch.deferred.append(lambda: ran.append(2))                # (as if collected for a side stream)
+            sch.kept.append(())
+            sch.tn_pending.append((wgrad.TnPending(), ()))            # (as if a split sum were pending: its record, its destination, its scratch)
+            sch.tn_ptrs.add(0x1000)
+            sch.tn_arena[0][1:] = [1, 4096]
             raise ValueError("step failed")
-    assert ran == [1] and not ops._SIDE_DEFERRED and not ops._SIDE_PENDING and ops.WGRAD_STREAM is prev
+    assert ran == [1] and not sch.deferred and not sch.kept and wgrad.stream() is prev
+    assert not sch.tn_pending and not sch.tn_ptrs and sch.tn_arena[0][1:] == [0, 0]
+
+
+def test_without_a_side_stream_the_scheduler_runs_launches_inline_and_synchronises_nothing(monkeypatch):
+    """The single-stream path of every non-training caller: defer() runs its launch at once, settle() / join() / mark() / wait(None) do nothing
+    (no stream, no event, no library call), mark() hands back None, and on_stream() leaves the current stream alone."""
+    from cxrmate_amd import wgrad
+    sch = wgrad.scheduler
+    assert wgrad.stream() is None and sch.exclusive_on
+    monkeypatch.setattr(wgrad.LIB, "call", lambda *a: pytest.fail(f"library call {a[0]} without a side stream"))
+    for name in ("Stream", "Event", "current_stream", "stream"):
+        monkeypatch.setattr(torch.cuda, name, lambda *a, _n=name, **k: pytest.fail(f"torch.cuda.{_n} without a side stream"))
+    ran = []
+    wgrad.defer(lambda: ran.append(1), torch.zeros(1))
+    assert ran == [1] and not sch.deferred and not sch.kept
+    wgrad.settle(); wgrad.join(); wgrad.begin()
+    assert wgrad.mark() is None and wgrad.wait(None) is None
+    with wgrad.on_stream(torch.zeros(1), None):
+        wgrad.defer(lambda: ran.append(2))
+    assert ran == [1, 2] and wgrad.stream() is None and sch.exclusive_on and not sch.tn_pending
 
 
 def test_pending_log_softmax_behaves_like_the_computed_tensor():

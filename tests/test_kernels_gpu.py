@@ -303,10 +303,10 @@ def test_gemm_tn_is_deterministic(ops, R, I, J):
 
 def test_deferred_weight_gradient_sums_equal_the_immediate_ones(ops):
     """Round 4: on the weight-gradient stream every split-K weight-gradient GEMM only leaves its partial tiles behind (scratch of its own) and ONE
-    batched launch adds all pending sums (cxr_gemm_tn_partial_bf16 + cxr_gemm_tn_reduce_batch, ops.wgrad_reduce). Same lanes, same split order as the
+    batched launch adds all pending sums (cxr_gemm_tn_partial_bf16 + cxr_gemm_tn_reduce_batch, wgrad.reduce). Same lanes, same split order as the
     per-GEMM reduce launches: the gradients -- 60 of them here (two batches), strided outputs, bias gradients, accumulation into non-zero buffers,
     the same output hit twice -- are bit-identical to the immediate path, and a second deferred round over the recycled scratch is too."""
-    from cxrmate_amd.training import wgrad_overlap
+    from cxrmate_amd import wgrad
     shapes = [(8192, 768, 768), (5000, 384, 1536), (3001, 200, 72), (9280, 384, 384), (4096, 64, 64), (6000, 192, 576), (2048, 3072, 768)]
     probs = []
     for n in range(60):
@@ -329,13 +329,13 @@ def test_deferred_weight_gradient_sums_equal_the_immediate_ones(ops):
         rounds = []
         for rnd_ in range(2):
             if deferred:
-                with wgrad_overlap():
+                with wgrad.overlap():
                     for (p, q, b, al), o, d in zip(probs, outs, dbs):
-                        ops.linear_bwd_weight(p, q, o[:, 4:4 + q.shape[1]], d) if al == 1.0 else ops._side_defer(
+                        ops.linear_bwd_weight(p, q, o[:, 4:4 + q.shape[1]], d) if al == 1.0 else wgrad.defer(
                             lambda p=p, q=q, o=o, d=d, al=al: ops.gemm_tn(p, q, o[:, 4:4 + q.shape[1]], dbias=d, alpha=al), p, q, o, d)
-                    ops.wgrad_flush()
-                    ops.wgrad_join()
-                    assert not ops._TN_PENDING
+                    wgrad.flush()
+                    wgrad.join()
+                    assert not wgrad.scheduler.tn_pending
             else:
                 for (p, q, b, al), o, d in zip(probs, outs, dbs):
                     ops.gemm_tn(p, q, o[:, 4:4 + q.shape[1]], dbias=d, alpha=al)
@@ -1157,14 +1157,13 @@ def test_batched_layout_and_mask_launches_equal_their_single_launch_forms(ops):
     _, st = ops.layernorm(x, g, g, 1e-5, need_stats=True)
     dg0, db0 = torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
     dx0 = ops.layernorm_bwd(x, dy, g, st, dg0, db0)
-    side = torch.cuda.Stream()
-    ops.WGRAD_STREAM = side
-    try:
-        dg1, db1 = torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
-        dx1 = ops.layernorm_bwd(x, dy, g, st, dg1, db1)                          # partial rows on this stream, row sum on the side stream
-        ops.wgrad_join()
-    finally:
-        ops.WGRAD_STREAM = None
+    from cxrmate_amd import wgrad
+    with wgrad.overlap():
+        try:
+            dg1, db1 = torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
+            dx1 = ops.layernorm_bwd(x, dy, g, st, dg1, db1)                      # partial rows on this stream, row sum on the side stream
+        finally:
+            wgrad.join()
     torch.cuda.synchronize()
     assert torch.equal(dx0, dx1)
     close(dg1, dg0, rtol=1e-5, atol=1e-4, what="dgamma via side-stream row sum"); close(db1, db0, rtol=1e-5, atol=1e-4, what="dbeta via side-stream row sum")

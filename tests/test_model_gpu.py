@@ -353,12 +353,12 @@ def test_training_step_gradients_do_not_depend_on_stream_overlap(M, monkeypatch)
     """The eager training step puts every weight-gradient kernel (and the embedding-table / LayerNorm parameter sums) on a side stream and joins
     it once per step: the gradients it leaves in the flat buffer must equal those of the same step issued on ONE stream (fp32 atomics reorder,
     nothing else), and the bf16-logits loss must match the fp32-logits loss."""
-    from cxrmate_amd import ops, training
+    from cxrmate_amd import training, wgrad
     g, cfg, sd, x, inp, lab, am, tt = gu.tf_single_case()
     res = {}
-    # overlap = the number of weight-gradient launches issued behind one fork event (ops._side_defer; 1000: only the joins flush), 0 = one stream
+    # overlap = the number of weight-gradient launches issued behind one fork event (wgrad.defer; 1000: only the joins flush), 0 = one stream
     for overlap in (4, 1, 1000, 0):
-        monkeypatch.setattr(ops, "_WGRAD_BATCH", max(overlap, 1))
+        monkeypatch.setattr(wgrad.scheduler, "batch", max(overlap, 1))
         m = M.SingleCXREncoderDecoderModel(cfg, seed=None)
         m.load_state_dict(sd)
         opt = training.FusedAdamW(m, lr=0.0)
@@ -366,16 +366,16 @@ def test_training_step_gradients_do_not_depend_on_stream_overlap(M, monkeypatch)
         args = (m, opt, x.cuda(), inp.cuda(), am.cuda(), ttd, lab.cuda(), gu.PAD, None, 0)
         for rep in range(3):                                      # repeated: a missing cross-stream dependency shows up as run-to-run noise
             if overlap:
-                with training.wgrad_overlap():
+                with wgrad.overlap():
                     loss, esaved, denc = training._phase_fwd_loss_decbwd(*args, join=False)
                     training._phase_encbwd(m, esaved, denc)
             else:
-                assert ops.WGRAD_STREAM is None
+                assert wgrad.stream() is None
                 loss, esaved, denc = training._phase_fwd_loss_decbwd(*args)
                 training._phase_encbwd(m, esaved, denc)
             torch.cuda.synchronize()
             res.setdefault(overlap, []).append((float(loss.item()), m.gflat.clone()))
-            assert not ops._SIDE_DEFERRED and not ops._SIDE_PENDING                    # every step ends flushed and joined
+            assert not wgrad.scheduler.deferred and not wgrad.scheduler.kept          # every step ends flushed and joined
     (l0, g0) = res[0][0]
     for l1, g1 in res[4] + res[1] + res[1000] + res[0][1:]:
         assert abs(l1 - l0) < 1e-5

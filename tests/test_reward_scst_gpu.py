@@ -221,8 +221,8 @@ def test_fused_sample_and_greedy_decode(cuda):
         dl = torch.zeros_like(lgs, dtype=torch.bfloat16)
         dl[:, :, 7] = 1.0
         m._dec.backward(saved, dlogits=dl.view(-1, dl.shape[-1]), need_denc=False)
-        ops_ = __import__("cxrmate_amd.ops", fromlist=["x"])
-        ops_.wgrad_join()
+        wgrad = __import__("cxrmate_amd.wgrad", fromlist=["x"])
+        wgrad.join()
         torch.cuda.synchronize()
         grads.append(m.gflat.clone())
     assert torch.allclose(grads[0], grads[1], rtol=1e-5, atol=1e-7)
@@ -240,7 +240,7 @@ def test_fused_sample_and_greedy_decode(cuda):
         dl[:, (t0 - frm):, 7] = 1.0
         dl[:, (t0 - frm):, 11] = -0.5
         m._dec.backward(saved, dlogits=dl.view(-1, dl.shape[-1]), need_denc=False)
-        ops_.wgrad_join()
+        wgrad.join()
         torch.cuda.synchronize()
         gsl.append(m.gflat.clone())
     assert torch.allclose(gsl[0], gsl[1], rtol=1e-4, atol=1e-6), float((gsl[0] - gsl[1]).abs().max())
@@ -258,12 +258,12 @@ def test_fused_sample_and_greedy_decode(cuda):
     dl[:, :, 7] = 1.0
     with pytest.raises(RuntimeError, match="another prefill"):
         m._dec.backward(saved, dlogits=dl.view(-1, dl.shape[-1]), need_denc=False)
-    ops_.wgrad_join()
+    wgrad.join()
     assert m._session_cross_kv(rec, enc16) is None                             # the same record can no longer borrow: the caller projects again
     m.zero_grads_prefix("decoder.")
     lgs, saved = m._dec.forward(tf_in, enc16, em8, (tf_in != gu.PAD).to(torch.uint8), tt, pos, save=True, cross_kv=m._session_cross_kv(rec, enc16))
     m._dec.backward(saved, dlogits=dl.view(-1, dl.shape[-1]), need_denc=False)
-    ops_.wgrad_join()
+    wgrad.join()
     torch.cuda.synchronize()
     assert torch.allclose(m.gflat, grads[0], rtol=1e-5, atol=1e-7)
     m.flat32.add_(0.0)                                                         # any in-place torch edit of the weights moves the stamp
