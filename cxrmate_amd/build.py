@@ -28,7 +28,7 @@ def _digest() -> str:
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(name.encode())
             h.update(f.read())
-    with open(os.path.join(os.path.dirname(HERE), "include", "cxrmate_hip.h"), "rb") as f:      # dwproj.hip includes the ABI header
+    with open(os.path.join(os.path.dirname(HERE), "include", "cxrmate_hip.h"), "rb") as f:      # every source includes the ABI header
         h.update(f.read())
     h.update(" ".join(FLAGS).encode())
     return h.hexdigest()

@@ -9,6 +9,7 @@
 // lives on ONE lane pair: softmax needs a single cross-lane exchange, and the exponentiated tile is already the
 // B operand of O^T += V^T.P^T (accumulator-as-operand, k-permutation per cdna_hip_programming.md section 3).
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 #include <stdlib.h>
 
 #define ATT_NEG (-1.0e30f)      // "masked" sentinel (finite: masked-only rows become uniform, like finfo.min in the reference)

@@ -7,6 +7,7 @@
 // Tiles that are consumed both row-wise (ds_read_b128) and column-wise (ds_read_b64_tr_b16) are kept as two LDS images
 // (144-B rows / 192-B rows) so both read patterns are bank-conflict free.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 #include <stdlib.h>
 
 struct AttnBwdArgs {

@@ -24,6 +24,7 @@
 // output is already normalised), or LayerNorm(gamma, beta, eps) of them with the row mean and variance computed here, in fp32, over the row
 // (two passes: mean, then centred squares) -- independent of the producers' partial-statistics format. Same row permutation.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 struct DecProbArgs {
     const bf16_t* Q; const bf16_t* K; const unsigned char* kpm; float* P; const uint32_t* drop_seed;

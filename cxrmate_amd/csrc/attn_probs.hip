@@ -16,6 +16,7 @@
 // each tile (32 rows x 64 keys fp32, 8 KB) goes through an XOR-swizzled LDS tile so that every global store is 16 bytes per lane and a
 // full 256-byte row segment per 16 lanes.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 #define ATT_NEG (-1.0e30f)            // attention.hip's masked-score sentinel (log2 units)
 

@@ -13,6 +13,7 @@
 //   zeros inside the max. floor[pair][0] != 0 floors the row maxima at 0 (this pair's ref is shorter than its chunk's longest ref), floor[pair][1]
 //   the column maxima (this pair's hyp is shorter than its chunk's longest hyp). The host computes both.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 namespace {
 

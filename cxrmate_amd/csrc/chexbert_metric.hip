@@ -13,6 +13,7 @@
 // A study whose offsets or row indices point outside their tables gets NaN in all its outputs (nothing is read through the index); the NaN then
 // reaches every column sum, as it should: such a table has no scores.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 namespace {
 

@@ -21,6 +21,7 @@
 // their arrays gets NaN. The offsets of both streams are validated on the host before anything is launched (one small copy and a stream wait: this
 // is an epoch-end call), so no kernel reads through an unchecked offset.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 #include <vector>
 
@@ -28,7 +29,7 @@
 
 namespace {
 
-constexpr int NLG_MAX_LEN = 8192;                 // longest supported text, in tokens of either stream
+constexpr int NLG_MAX_LEN = CXR_COCO_NLG_MAX_LEN; // longest supported text, in tokens of either stream
 constexpr int NLG_THREADS = 256;
 constexpr int NLG_COLS = 6;                       // bleu_1..4, rouge, cider
 constexpr int NLG_INTS = 9;                       // len_hyp, len_ref, c_1..c_4, lcs, rouge len_hyp, rouge len_ref

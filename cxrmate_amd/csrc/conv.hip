@@ -5,6 +5,7 @@
 //   * its backward (input gradient + per-channel tap/shift gradient sums)
 // These are HBM-bound: channel-contiguous 16-byte accesses, taps re-read through L1/L2.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 // ---------------------------------------------------------------------------------------------- stage-1 im2col
 // pixels [Bn, Cin, H, W] fp32 NCHW  ->  col [Bn*Ho*Wo, Kpad] bf16, k = c*KS*KS + ky*KS + kx (= weight.view(Cout,-1)), zero padded

@@ -1,6 +1,7 @@
 // Autoregressive-decode helpers: beam reordering of the self-attention KV cache and the
 // top-2*beams continuation search of beam search (TF5 generation/utils.py:3388-3435).
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 #include <stdlib.h>
 
 #ifndef CXR_STAMP

@@ -3,6 +3,7 @@
 // The keep decision is a pure function of (seed, site, b, t, col) -- common.h -- so backward and the teacher-forced re-scoring of a sampled
 // sequence regenerate the forward masks instead of storing them.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 // out[r, :] = (resid ? resid[r, :] : 0) + f(r, :) * y[r, :]
 //   element mode (row_scale == NULL): f = keep(seed, site, b, t, col) / (1 - p),  b = r / rows_per_b, t = t0 + r % rows_per_b

@@ -14,6 +14,7 @@
 // conditional loads: hipcc parks s_waitcnt vmcnt(0) behind a guarded load) and dropped on the store side.
 // Epilogue: bias, GELU, residual (bf16), output as bf16 and / or as e4m3 with its own scale (the next fp8 layer's input: no quantisation pass).
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 namespace {
 

@@ -4,6 +4,7 @@
 // a copy of the (already processed) rows or their log_softmax. Output rows can be permuted from the beam-major order of the device decode
 // (row = beam * S + study) to the study-major order the library returns (study * nb + beam). No host reads, no allocation: capturable.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 constexpr int GR_THREADS = 256;
 

@@ -3,9 +3,10 @@
 // absolute min_length by the caller), applied in that order (TF5 generation/utils.py:1174-1235) to fp32 score rows in place. The history of
 // row r is ids[r, 0 .. cur): the whole running sequence (BOS, prompt, generated tokens). No host reads, no allocation: capturable.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 constexpr int LP_THREADS = 256;
-constexpr int LP_MAX_HIST = 512;          // history ids per row (the decoder's position table)
+constexpr int LP_MAX_HIST = CXR_LOGITS_PROC_MAX_HIST;   // history ids per row (the decoder's position table)
 constexpr int LP_PER_THREAD = LP_MAX_HIST / LP_THREADS;
 
 // The three controls as device functions, shared by both kernels below. x: the row's scores, h: its history ids[r, 0 .. cur).

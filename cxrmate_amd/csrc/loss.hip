@@ -2,6 +2,7 @@
 // greedy argmax (lowest index wins ties, like torch.argmax), and top-k multinomial sampling. One 256-thread block per logits row
 // (V = 30000 fp32 = 120 KB: first pass from HBM, later passes from L2).
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 #ifndef CXR_STAMP
 #define CXR_STAMP(i)            /* scripts/lab defines it to record s_memrealtime per wave; nothing in the product build */
 #endif

@@ -1,5 +1,6 @@
 // Gather / integer / optimiser kernels of the CXRMate hot path.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
 extern "C" { int g_cxr_last_hip_error = 0; }
 extern "C" int cxr_last_hip_error() { return g_cxr_last_hip_error; }                       // hipError_t of the last failed launch

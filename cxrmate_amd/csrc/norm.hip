@@ -3,6 +3,7 @@
 // HBM-bound: 16-byte vector loads, a row is owned by a group of LPR lanes of one wave (wave-shuffle reductions),
 // several rows per wave when C is small (C=64 -> 8 rows per wave) so that every lane issues a full 16-byte access.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 #include <stdlib.h>
 
 template <int C, bool LN_TRI = false> struct LNCfg {

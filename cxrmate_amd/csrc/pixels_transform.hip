@@ -16,9 +16,10 @@
 // Nothing a descriptor or table says is trusted with an address: a descriptor that does not fit its buffers disables its image (NaN / 0 output),
 // and every tap range is clamped to its row.
 #include "common.h"
+#include "../../include/cxrmate_hip.h"
 
-#define IT_DESC_INTS 24                       // int32 per image, see include/cxrmate_hip.h
-#define IT_BAND_BYTES 49152                   // LDS per workgroup of the horizontal pass; a source row (pitch) must fit
+#define IT_DESC_INTS CXR_IMAGE_TRANSFORM_DESC_INTS       // int32 per image, see include/cxrmate_hip.h
+#define IT_BAND_BYTES CXR_IMAGE_TRANSFORM_BAND_BYTES     // LDS per workgroup of the horizontal pass; a source row (pitch) must fit
 #define IT_ROWS_PER_THREAD 8
 #define IT_PREC 22
 

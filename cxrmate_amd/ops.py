@@ -10,7 +10,7 @@ import gc
 import torch
 
 from . import wgrad
-from ._lib import LIB, CxrError
+from ._lib import LIB, LIMITS, STRUCTS, CxrError
 from .wgrad import raw_stream as _s
 
 BF16 = torch.bfloat16
@@ -70,13 +70,7 @@ def gemm_nt(a, w, bias=None, residual=None, act=0, aux=None, out=None, out_f32=F
 _GEMM_GROUP = __import__("os").environ.get("CXR_GEMM_GROUP", "1") != "0"
 
 
-class _GemmNtDesc(_ct.Structure):
-    """Mirror of `cxr_gemm_nt_desc` (include/cxrmate_hip.h)."""
-    _fields_ = [("A", _ct.c_void_p), ("lda", _ct.c_long), ("W", _ct.c_void_p), ("ldw", _ct.c_long), ("C", _ct.c_void_p), ("ldc", _ct.c_long),
-                ("bias", _ct.c_void_p), ("residual", _ct.c_void_p), ("ldr", _ct.c_long), ("aux", _ct.c_void_p), ("ldaux", _ct.c_long),
-                ("M", _ct.c_int), ("N", _ct.c_int), ("K", _ct.c_int), ("alpha", _ct.c_float), ("act", _ct.c_int), ("out_f32", _ct.c_int),
-                ("accumulate", _ct.c_int), ("drop_p", _ct.c_float), ("drop_seed", _ct.c_void_p), ("drop_site", _ct.c_uint),
-                ("drop_rows_per_b", _ct.c_int), ("drop_t0", _ct.c_int), ("row_scale", _ct.c_void_p), ("rs_rows", _ct.c_int), ("rs_after", _ct.c_int)]
+_GemmNtDesc = STRUCTS["cxr_gemm_nt_desc"]
 
 
 def gemm_nt_group(problems):
@@ -624,15 +618,7 @@ def tap_grad_accum(G, dw):
 
 
 # ---- fused query / key / value convolutional projections (csrc/dwproj.hip): one LDS-staged pass per layer and step of the BatchNorm algebra
-class DwProj(_ct.Structure):
-    """Mirror of `cxr_dwproj` (include/cxrmate_hip.h): one depthwise projection of the shared activation; device pointers as integers."""
-    _fields_ = [("stride", _ct.c_int), ("taps", _ct.c_void_p), ("shift", _ct.c_void_p), ("y", _ct.c_void_p), ("y_bs", _ct.c_long), ("y_rs", _ct.c_long),
-                ("w", _ct.c_void_p), ("gamma", _ct.c_void_p), ("beta", _ct.c_void_p), ("run_mean", _ct.c_void_p), ("run_var", _ct.c_void_p),
-                ("mean", _ct.c_void_p), ("rstd", _ct.c_void_p), ("taps_out", _ct.c_void_p), ("shift_out", _ct.c_void_p),
-                ("dgamma", _ct.c_void_p), ("dbeta", _ct.c_void_p), ("coef", _ct.c_void_p), ("GS", _ct.c_void_p), ("dw", _ct.c_void_p),
-                ("yf", _ct.c_void_p), ("yf_bs", _ct.c_long), ("yf_rs", _ct.c_long)]
-
-
+DwProj = STRUCTS["cxr_dwproj"]      # one depthwise projection of the shared activation; device pointers as integers
 _DWP_PTRS = ("taps", "shift", "w", "gamma", "beta", "run_mean", "run_var", "mean", "rstd", "taps_out", "shift_out", "dgamma", "dbeta", "coef", "GS", "dw")
 _DWP_WS = {}
 
@@ -906,7 +892,7 @@ def log_softmax_rows_(x, add_row=None):
     return x
 
 
-LOGITS_PROCESS_MAX_HIST = 512
+LOGITS_PROCESS_MAX_HIST = LIMITS["CXR_LOGITS_PROC_MAX_HIST"]
 
 
 def logits_process_(scores, ids, cur, eos=-1, penalty=1.0, ngram=0, min_length=0):
@@ -1287,19 +1273,7 @@ def dal_rows(M):
     return 16 * (4 if t == 3 else t)
 
 
-class _DecProb(_ct.Structure):
-    """Mirror of `cxr_dec_gemm_prob` (include/cxrmate_hip.h)."""
-    _fields_ = [("Wp", _ct.c_void_p), ("bc", _ct.c_void_p), ("C", _ct.c_void_p), ("ldc", _ct.c_long), ("N", _ct.c_int), ("c_dal", _ct.c_int),
-                ("fold", _ct.c_int), ("no_bias", _ct.c_int), ("lr_Ap", _ct.c_void_p), ("lr_B", _ct.c_void_p), ("lr_site", _ct.c_uint)]
-
-
-class _DecDesc(_ct.Structure):
-    """Mirror of `cxr_dec_gemm_desc`."""
-    _fields_ = [("A", _ct.c_void_p), ("M", _ct.c_int), ("K", _ct.c_int), ("nprob", _ct.c_int), ("act", _ct.c_int), ("out_f32", _ct.c_int),
-                ("nc_hint", _ct.c_int), ("mt_hint", _ct.c_int), ("p", _DecProb * 3), ("stats", _ct.c_void_p), ("stats_tiles", _ct.c_int), ("eps", _ct.c_float),
-                ("residual", _ct.c_void_p), ("ldr", _ct.c_long), ("rgb", _ct.c_void_p), ("out_stats", _ct.c_void_p),
-                ("drop_p", _ct.c_float), ("drop_seed", _ct.c_void_p), ("drop_site", _ct.c_uint), ("drop_t", _ct.c_int),
-                ("lr_p", _ct.c_float), ("lr_seed", _ct.c_void_p), ("lr_scale", _ct.c_float), ("lr_t", _ct.c_int)]
+_DecProb, _DecDesc = STRUCTS["cxr_dec_gemm_prob"], STRUCTS["cxr_dec_gemm_desc"]
 
 
 def dec_pack_weight(w, gamma=None, beta=None, bias=None, out=None):
@@ -1427,22 +1401,7 @@ def lora_up_add_(y, t, W, w_is_b, drop=None, rows_per_b=1, tpos0=0, seed=None):
     return y
 
 
-class _LoraDownDesc(_ct.Structure):
-    """Mirror of `cxr_lora_down_desc` (include/cxrmate_hip.h)."""
-    _fields_ = [("x", _ct.c_void_p), ("ldx", _ct.c_long), ("W", _ct.c_void_p), ("w_rs", _ct.c_long), ("w_cs", _ct.c_long), ("t", _ct.c_void_p),
-                ("p", _ct.c_float), ("site", _ct.c_uint)]
-
-
-class _LoraUpDesc(_ct.Structure):
-    """Mirror of `cxr_lora_up_desc`."""
-    _fields_ = [("y", _ct.c_void_p), ("ldy", _ct.c_long), ("t", _ct.c_void_p), ("W", _ct.c_void_p), ("w_rs", _ct.c_long), ("w_cs", _ct.c_long),
-                ("p", _ct.c_float), ("site", _ct.c_uint)]
-
-
-class _LoraOuterDesc(_ct.Structure):
-    """Mirror of `cxr_lora_outer_desc`."""
-    _fields_ = [("a", _ct.c_void_p), ("lda", _ct.c_long), ("t", _ct.c_void_p), ("G", _ct.c_void_p), ("g_ks", _ct.c_long), ("g_rs", _ct.c_long),
-                ("p", _ct.c_float), ("site", _ct.c_uint)]
+_LoraDownDesc, _LoraUpDesc, _LoraOuterDesc = STRUCTS["cxr_lora_down_desc"], STRUCTS["cxr_lora_up_desc"], STRUCTS["cxr_lora_outer_desc"]
 
 
 def _lora_w_strides(W, w_is_b):
@@ -1536,7 +1495,7 @@ def chexbert_scores(pred, ref, pred_row, ref_row, study_off):
     return example, cls, avg
 
 
-COCO_NLG_MAX_LEN = 8192
+COCO_NLG_MAX_LEN = LIMITS["CXR_COCO_NLG_MAX_LEN"]
 
 
 def coco_nlg_workspace_bytes(n_ids_a, M):
@@ -1577,8 +1536,8 @@ def coco_nlg_scores(ids_a, off_a, ids_b, off_b, pairs, ref_mult, order, study_of
     return scores, ints, study, avg
 
 
-IMAGE_TRANSFORM_DESC_INTS = 24
-IMAGE_TRANSFORM_BAND_BYTES = 49152
+IMAGE_TRANSFORM_DESC_INTS = LIMITS["CXR_IMAGE_TRANSFORM_DESC_INTS"]
+IMAGE_TRANSFORM_BAND_BYTES = LIMITS["CXR_IMAGE_TRANSFORM_BAND_BYTES"]
 
 
 def image_transform_workspace_bytes(inter):

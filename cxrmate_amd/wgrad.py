@@ -10,7 +10,7 @@ import warnings
 
 import torch
 
-from ._lib import LIB
+from ._lib import LIB, STRUCTS
 
 _DEV_INDEX = None
 _RAW_OVERRIDE = None    # raw handle of the weight-gradient stream while flush() issues collected launches
@@ -26,11 +26,7 @@ def raw_stream():
     return torch._C._cuda_getCurrentRawStream(_DEV_INDEX)
 
 
-class TnPending(_ct.Structure):
-    """cxr_tn_pending (include/cxrmate_hip.h): a weight gradient whose sum over the token splits is still to be added to C / dbias"""
-    _fields_ = [("ws", _ct.c_void_p), ("wsb", _ct.c_void_p), ("C", _ct.c_void_p), ("dbias", _ct.c_void_p), ("ldc", _ct.c_long),
-                ("I", _ct.c_int), ("J", _ct.c_int), ("Ip", _ct.c_int), ("Jp", _ct.c_int), ("splits", _ct.c_int), ("reserved", _ct.c_int)]
-
+TnPending = STRUCTS["cxr_tn_pending"]     # a weight gradient whose sum over the token splits is still to be added to C / dbias
 
 _TN_WS_FLOATS = 16 << 20    # scratch of the immediate path: 16 M floats (64 MB) cover every shape of this model
 _TN_CHUNK = 64 << 20        # floats per arena buffer of the deferred path (256 MB)

@@ -20,6 +20,13 @@ extern "C" {
 
 typedef struct ihipStream_t* hipStream_t;
 
+/* Limits that the kernels and their callers share. The kernels' constants are defined from these; cxrmate_amd/_lib.py reads the integer
+ * `#define CXR_...` lines (and the struct typedefs below) with the parser that reads the prototypes. */
+#define CXR_COCO_NLG_MAX_LEN 8192              /* cxr_coco_nlg_scores: longest text, in tokens of either stream */
+#define CXR_LOGITS_PROC_MAX_HIST 512           /* cxr_logits_process_f32 / cxr_logits_constrain_f32: history ids per row */
+#define CXR_IMAGE_TRANSFORM_DESC_INTS 24       /* cxr_image_transform: int32 per image descriptor */
+#define CXR_IMAGE_TRANSFORM_BAND_BYTES 49152   /* cxr_image_transform: LDS of a horizontal-pass workgroup = the longest source row pitch */
+
 /* ---- dense contractions ------------------------------------------------------------------------------------------------
  * C[M,N] = epi(alpha * A[M,K] . W[N,K]^T): every nn.Linear of CvT (TF5:cvt:171-173,224,274-293), the projection head
  * (REF:modules/transformers/single_model/modelling_single.py:25-40), BERT q/k/v/o/FFN/LM head (TF5:bert:164-203,289-351,466-496),
@@ -326,7 +333,7 @@ int cxr_log_softmax_rows(float* x, long ld, long R, int V, const float* add_row,
 
 /* ---- generation controls (TF5 logits_process.py: RepetitionPenalty :306, NoRepeatNGram :1021-1110, MinLength :101 / MinNewTokens :164, in
  * the order of TF5:gen:1174-1235). In place on fp32 score rows logits [R, V] (raw logits, or log-probs on the beam path); ids int64 [R, ids_ld],
- * history = columns [0, cur), cur <= 512. penalty 1 = off (else > 0: x < 0 ? x * penalty : x / penalty on every history id, once), ngram 0 =
+ * history = columns [0, cur), cur <= CXR_LOGITS_PROC_MAX_HIST. penalty 1 = off (else > 0: x < 0 ? x * penalty : x / penalty on every history id, once), ngram 0 =
  * off (ids completing an n-gram of the history -> -inf; nothing while cur < ngram), eos -> -inf while cur < min_length (absolute length, the
  * caller folds min_new_tokens in). One workgroup per row; capturable. */
 int cxr_logits_process_f32(float* logits, long ld, const long* ids, long ids_ld, long R, int V, int cur, long eos, float penalty, int ngram,
@@ -516,8 +523,8 @@ int cxr_pixels_u8_to_f32(const void* src, const long* first_image, float* dst, i
  * RandomRotation (train) + ToTensor + Normalize + pad_sequence from the DECODED full-size uint8 images, byte-identical to Pillow's antialiased
  * bilinear Image.resize and nearest-neighbour Image.rotate (integer arithmetic only; the host builds the tables: cxrmate_amd/pixels.py).
  * src: the images packed into one buffer, grey [H][pitch] or interleaved RGB, each at a 16-byte aligned offset with a row pitch that is a multiple
- * of 16 and at most 49152 bytes. desc int32: [n_images][24] descriptors, then slot_image [B*Nmax] (the image of slot [b, n], -1 = absent), then
- * bands [n_bands][2] = (image, first source row) of every workgroup of the horizontal pass (rows 0, r, 2r, ... with r = 49152 / pitch).
+ * of 16 and at most CXR_IMAGE_TRANSFORM_BAND_BYTES bytes. desc int32: [n_images][CXR_IMAGE_TRANSFORM_DESC_INTS] descriptors, then slot_image [B*Nmax] (the image of slot [b, n], -1 = absent), then
+ * bands [n_bands][2] = (image, first source row) of every workgroup of the horizontal pass (rows 0, r, 2r, ... with r = CXR_IMAGE_TRANSFORM_BAND_BYTES / pitch).
  * Descriptor: 0 source offset / 16, 1 H, 2 W, 3 C (1 or 3), 4 pitch, 5 oh, 6 ow (resized size), 7 top, 8 left (crop), 9 / 10 horizontal table
  * offset into `tables` and its ksize, 11 / 12 the vertical table's, 13 intermediate offset / 16 in the workspace (uint8 [H][ow][C]), 14-15 unused,
  * 16-21 a0..a5: output pixel (x, y) of the S x S crop reads crop pixel ((a2 + a1 y + a0 x) >> 16, (a5 + a4 y + a3 x) >> 16), 0 outside (Pillow's
@@ -566,8 +573,8 @@ int cxr_chexbert_scores(const long* pred, int n_pred, const long* ref, int n_ref
  * that text (its weight in CIDEr's document frequency); order int32 [M] = the records grouped by study, study_off int32 [S+1] = CSR offsets into
  * it. -> scores [M][6] = bleu_1..4, rouge, cider; ints int32 [M][9] = len_hyp, len_ref, clipped 1..4-gram matches, lcs, the two ROUGE lengths;
  * study [S][6] = mean over a study's records; avg [6] = mean over the studies. N-gram identity is exact for any int32 vocabulary; every
- * floating-point sum has a fixed order and there are no floating-point atomics, so repeated launches are bit-identical. A text longer than 8192
- * tokens, malformed offsets or a short workspace return -1 before anything is launched (the offsets are checked on the host: the call waits for
+ * floating-point sum has a fixed order and there are no floating-point atomics, so repeated launches are bit-identical. A text longer than
+ * CXR_COCO_NLG_MAX_LEN tokens, malformed offsets or a short workspace return -1 before anything is launched (the offsets are checked on the host: the call waits for
  * the stream once). A record with a text index outside [0, n_texts) gets NaN scores and -1 integers; a study with offsets or record indices
  * outside their arrays gets NaN. M == 0 and S == 0 are accepted (avg is then NaN). workspace: cap * 12 + 3 * round_up(4 * n_ids_a, 8) + 32 * M
  * bytes, cap = the power of two >= max(1024, 2 * n_ids_a); 8-byte aligned. */
@@ -597,6 +604,7 @@ int cxr_cosine_rows_f32(const float* a, long lda, const float* b, long ldb, floa
 
 /* hipError_t of the most recent failed launch (return code -2); cxr_last_hip_error_string() gives its text */
 int cxr_last_hip_error(void);
+const char* cxr_last_hip_error_string(void);
 
 /* ---- optimiser and plumbing (REF:modules/lightning_modules/single.py:426-431 torch.optim.AdamW defaults) ------------------ */
 int cxr_adamw_step(float* p, const float* g, float* m, float* v, void* p16, long n, float lr, float b1, float b2, float eps, float wd, int step,

@@ -33,6 +33,117 @@ def test_library_exports_every_declared_symbol(built_lib):
         assert all(t in (ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_uint, ctypes.c_float) for t, _ in args), name
 
 
+HEADER_STRUCTS = ("cxr_gemm_nt_desc", "cxr_tn_pending", "cxr_lora_down_desc", "cxr_lora_up_desc", "cxr_lora_outer_desc", "cxr_dwproj",
+                  "cxr_dec_gemm_prob", "cxr_dec_gemm_desc")
+
+
+def test_parsed_struct_layouts_equal_the_c_compilers(tmp_path):
+    """sizeof and every field's offsetof / size, as the host C compiler lays the header's structs out, against the ctypes classes that
+    _lib.parse_structs() builds from the same header (the classes every descriptor of ops / wgrad is an instance of)."""
+    import ctypes
+    import shutil
+    from cxrmate_amd import _lib
+    structs = _lib.parse_structs()
+    assert tuple(structs) == HEADER_STRUCTS
+    cc = shutil.which(os.environ.get("CC", "cc")) or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no host C compiler"
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{_lib.HEADER}"', 'int main(void) {']
+    for name, cls in structs.items():
+        lines.append(f'    printf("{name} sizeof %zu 0\\n", sizeof({name}));')
+        for field, _ in cls._fields_:
+            lines.append(f'    printf("{name} {field} %zu %zu\\n", offsetof({name}, {field}), sizeof((({name}*)0)->{field}));')
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "abi_layout.c", tmp_path / "abi_layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], check=True, capture_output=True, text=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    compiled = {(s, f): (int(a), int(b)) for s, f, a, b in (line.split() for line in out.splitlines())}
+    parsed = {}
+    for name, cls in structs.items():
+        parsed[(name, "sizeof")] = (ctypes.sizeof(cls), 0)
+        for field, _ in cls._fields_:
+            parsed[(name, field)] = (getattr(cls, field).offset, getattr(cls, field).size)
+    assert sum(len(cls._fields_) for cls in structs.values()) == 119 and len(parsed) == 119 + 8
+    assert parsed == compiled, {k: (parsed.get(k), compiled.get(k)) for k in set(parsed) | set(compiled) if parsed.get(k) != compiled.get(k)}
+    # the embedded array and what follows it
+    desc, prob = structs["cxr_dec_gemm_desc"], structs["cxr_dec_gemm_prob"]
+    assert desc.p.size == 3 * ctypes.sizeof(prob) and desc.stats.offset == desc.p.offset + desc.p.size
+    # the names ops / wgrad use are these classes, not copies
+    from cxrmate_amd import ops, wgrad
+    assert [ops._GemmNtDesc, wgrad.TnPending, ops._LoraDownDesc, ops._LoraUpDesc, ops._LoraOuterDesc, ops.DwProj, ops._DecProb, ops._DecDesc] \
+        == [_lib.STRUCTS[n] for n in HEADER_STRUCTS]
+
+
+def test_struct_parser_misses_nothing_and_refuses_what_it_does_not_understand():
+    import ctypes
+    import re
+    from cxrmate_amd import _lib
+    text = open(_lib.HEADER).read()
+    assert len(_lib.parse_structs()) == len(re.findall(r"typedef struct cxr_", text)) == 8
+    ok = _lib.parse_structs("typedef struct cxr_a { const int x; /* c; */ unsigned int u, v[2]; float f; long l; } cxr_a;\n"
+                            "typedef struct cxr_b { cxr_a q[3]; const void* p; const unsigned int* s; float* t; } cxr_b;")
+    assert [(f, t._length_ if hasattr(t, "_length_") else t) for f, t in ok["cxr_a"]._fields_] == \
+        [("x", ctypes.c_int), ("u", ctypes.c_uint), ("v", 2), ("f", ctypes.c_float), ("l", ctypes.c_long)]
+    assert ok["cxr_b"].q.size == 3 * ctypes.sizeof(ok["cxr_a"]) and [t for _, t in ok["cxr_b"]._fields_[1:]] == [ctypes.c_void_p] * 3
+    for field in ("int flags : 3;", "double x;", "float *a, *b;", "int (*fn)(int);", "struct { int y; } z;", "cxr_later q;", "char c;", "int n[];",
+                  "unsigned u;", "int a b;"):
+        with pytest.raises(ValueError):
+            _lib.parse_structs("typedef struct cxr_a { int before; " + field + " int after; } cxr_a;")
+    with pytest.raises(ValueError):
+        _lib.parse_structs("typedef struct cxr_a { int x; } cxr_other;")
+
+
+def test_every_source_sees_the_header_and_every_prototype_has_one_definition():
+    import re
+    from cxrmate_amd import _lib, build
+    assert len(build.SOURCES) == 24
+    texts = {s: open(os.path.join(build.CSRC, s)).read() for s in build.SOURCES}
+    for src, text in texts.items():
+        inc = text.find('#include "../../include/cxrmate_hip.h"')
+        assert inc >= 0, f"{src} does not include the ABI header"
+        first = re.search(r'extern\s+"C"\s+[^;{]*\bcxr_\w+\s*\([^)]*\)\s*\{', text)
+        assert first and inc < first.start(), f"{src}: the ABI header must come before the first extern \"C\" definition"
+    protos = _lib.parse_header()
+    for name in list(protos) + ["cxr_last_hip_error_string"]:
+        pat = re.compile(r'extern\s+"C"\s+(?:int|const\s+char\s*\*)\s*' + name + r'\s*\([^)]*\)\s*\{')
+        owners = [src for src, text in texts.items() for _ in pat.finditer(text)]
+        assert len(owners) == 1, (name, owners)
+    assert re.search(r"\bconst char\* cxr_last_hip_error_string\(void\);", open(_lib.HEADER).read())
+    assert "cxr_last_hip_error_string" not in protos          # not an `int` prototype: _Lib.call sets its restype by hand
+
+
+def test_no_module_but_lib_defines_a_ctypes_structure():
+    import ctypes
+    import importlib
+    import pkgutil
+    import cxrmate_amd
+    walked = [importlib.import_module(info.name) for info in pkgutil.walk_packages(cxrmate_amd.__path__, "cxrmate_amd.")]
+    assert len(walked) >= 10
+
+    def subclasses(cls):
+        return [s for c in cls.__subclasses__() for s in [c] + subclasses(c)]
+    ours = {c for base in (ctypes.Structure, ctypes.Union) for c in subclasses(base) if c.__module__.split(".")[0] == "cxrmate_amd"}
+    assert len(ours) >= 8 and {c.__module__ for c in ours} == {"cxrmate_amd._lib"}, sorted((c.__module__, c.__name__) for c in ours)
+    for sub in ("ops.py", "wgrad.py"):      # and not by another route either
+        assert "_fields_" not in open(os.path.join(os.path.dirname(cxrmate_amd.__file__), sub)).read()
+
+
+def test_shared_limits_come_from_the_header_macros():
+    import re
+    from cxrmate_amd import _lib, build, ops
+    limits = _lib.parse_limits()
+    assert limits == _lib.LIMITS == {"CXR_COCO_NLG_MAX_LEN": 8192, "CXR_LOGITS_PROC_MAX_HIST": 512, "CXR_IMAGE_TRANSFORM_DESC_INTS": 24,
+                                     "CXR_IMAGE_TRANSFORM_BAND_BYTES": 49152}
+    for const, macro, src, kernel_name in (("COCO_NLG_MAX_LEN", "CXR_COCO_NLG_MAX_LEN", "coco_nlg.hip", "NLG_MAX_LEN"),
+                                           ("LOGITS_PROCESS_MAX_HIST", "CXR_LOGITS_PROC_MAX_HIST", "logits_proc.hip", "LP_MAX_HIST"),
+                                           ("IMAGE_TRANSFORM_DESC_INTS", "CXR_IMAGE_TRANSFORM_DESC_INTS", "pixels_transform.hip", "IT_DESC_INTS"),
+                                           ("IMAGE_TRANSFORM_BAND_BYTES", "CXR_IMAGE_TRANSFORM_BAND_BYTES", "pixels_transform.hip", "IT_BAND_BYTES")):
+        assert getattr(ops, const) == limits[macro]
+        text = open(os.path.join(build.CSRC, src)).read()
+        assert re.search(r"\b" + kernel_name + r"\s*=?\s*" + macro + r"\b", text), (src, macro)      # the kernel's constant is DEFINED from the macro
+    assert _lib.parse_limits("#define CXR_A 7\n  #  define CXR_B -3   \n#define CXR_MAIN_PRIO(x) 3\n#define CXR_F 1.5f\n#define OTHER 4\n") == {"CXR_A": 7, "CXR_B": -3}
+
+
 def test_product_fails_loudly_without_library(monkeypatch):
     from cxrmate_amd import _lib
     fresh = _lib._Lib()
